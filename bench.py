@@ -23,7 +23,11 @@ Multi-GPU: the path shards over independent sub-matrices (reference cli/chromosi
 so every rank processes its own map (weak scaling) with no data-path collective; the job
 throughput is N * pixels * steps / max-over-ranks time.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `ms_per_step` is the wall time of one of the `--steps` timed steps.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the arrays a caller of the
+timed path receives -- as DIR/<name>.npy (float32 / float64; an output above its share of 48 MiB keeps a fixed, seeded
+sample of its rows).  The inputs are seeded: two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -33,10 +37,7 @@ import os
 import sys
 import time
 
-# (before anything initialises HIP -- torch.distributed with N > 1, the library with N = 1: chromosight_amd/__init__.py says why)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-import numpy as np  # noqa: E402
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -59,6 +60,9 @@ def parse():
     ap.add_argument("--size", type=int, default=4096, help="c2 only: side of the dense map (default 4096)")
     ap.add_argument("--plan", action="store_true",
                     help="no GPU work: print the block -> rank assignment of the sharded C4 genome for --gpus N and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64; "
+                         "a fixed seeded row sample of a larger output, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -158,6 +162,11 @@ class Workload:
         self.engine.run_normxcorr2(self.dev, self.sig, self.shape, self.kspec, self.out,
                                    precision=self.precision, **self.kwargs)
 
+    def outputs(self):
+        """What the last step left for its caller: the coefficient map, n x n (c2) or n rows x max_dist + 1 diagonals (band)."""
+        width = self.shape[1] if self.name == "c2" else self.kwargs["max_dist"] + 1
+        return {f"{self.name}_corr": self.out_buf.download()[:, :width]}
+
 
 # cs_last_kernel() ids (include/chromosight_hip.h) -> what served the launch
 KERNELS = {
@@ -215,6 +224,27 @@ def time_steps(dev, step, sync, steps, warmup, dist=None, local_rank=0):
         dist.barrier(device_ids=[local_rank])
     elapsed = time.perf_counter() - t0
     return elapsed, dev.elapsed_ms(ev0, ev1) / steps
+
+
+DUMP_BYTES = 48 * 2 ** 20       # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: each array as `dirpath/<name>.npy`, float32 kept, anything else as float64.  An array above its
+    share of DUMP_BYTES keeps a fixed sample of its rows (seeded, in row order), the same from run to run and build to build.
+    Returns {name: shape written} for the result line."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64))
+        if a.nbytes > share:
+            keep = max(1, share // max(a.nbytes // a.shape[0], 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(dirpath, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def wide_template(k):
@@ -539,8 +569,9 @@ class GenomeC4:
         return rec_l, rec_b
 
 
-def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup):
-    """Time `steps` passes of the sharded C4 genome; returns the summary dict (same on every rank)."""
+def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup, outputs=None):
+    """Time `steps` passes of the sharded C4 genome; returns the summary dict (same on every rank).  `outputs` (a dict):
+    receives the record tables of the last timed step."""
     g = GenomeC4(args, rank, local_rank, world)
 
     def sync():
@@ -561,6 +592,8 @@ def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup):
         rec = g.step()
     sync()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(c4_loops_records=np.array(rec[0], dtype=np.float64), c4_borders_records=np.array(rec[1], dtype=np.float64))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -645,9 +678,11 @@ def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup):
 
 def run_c4(args, rank, local_rank, world, dist, torch):
     """C4 of BASELINE.md end to end, blocks sharded over the ranks (strong scaling)."""
-    r = time_genome(args, rank, local_rank, world, dist, torch, args.steps, args.warmup)
+    outputs = {} if args.dump_outputs else None
+    r = time_genome(args, rank, local_rank, world, dist, torch, args.steps, args.warmup, outputs)
     if rank == 0:
-        print(json.dumps({
+        dumped = {"dumped_outputs": dump_outputs(args.dump_outputs, outputs)} if outputs is not None else {}
+        print(json.dumps(dict({
             "metric": "Mpixels/s detect end to end (C4: 23 blocks, loops + 3 borders templates)",
             "value": r["value"], "unit": "Mpixel/s", "n_gpus": world, "steps": args.steps,
             "warmup": max(args.warmup, 1), "ms_per_step": r["ms_per_genome"], "higher_is_better": True,
@@ -657,17 +692,18 @@ def run_c4(args, rank, local_rank, world, dist, torch):
                        "stored_pixels_rank0": r["stored_pixels_rank0"],
                        "parallelism": f"{world} rank(s), {r['blocks']} blocks"},
             "patterns": r["patterns"], "setup": r["setup"],
-        }))
+        }, **dumped)))
 
 
-def time_c5(local_rank, world, dist, torch, steps, warmup):
+def time_c5(local_rank, world, dist, torch, steps, warmup, outputs=None):
     """C5 of BASELINE.md: `quantify --inter` with the three 11 x 11 borders templates on the committed 17-chromosome
     yeast map (tests/golden/yeast_cool.npz, the decoded .cool; positions = the fixture's: cohesin-peak pairs on the
     intra blocks, seeded positions on the inter blocks).  The pixel table is uploaded once (DeviceCool, reported under
     `setup`); one step = pipeline.quantify from the resident table: staging of every sub-matrix that holds a position
     (detrend / median scaling), one native call per template over all of them, best-of-templates selection.  N > 1: the
     sub-matrices are dealt to the ranks (parallel.quantify_genome: the reference's pool over sub-matrices), one exchange of
-    scores and windows, every rank assembles the table -- strong scaling of one fixed job.  Returns the leg's dictionary."""
+    scores and windows, every rank assembles the table -- strong scaling of one fixed job.  Returns the leg's dictionary;
+    `outputs` (a dict) receives the last timed step's table (its numeric columns) and windows."""
     import pandas as pd
     from chromosight_amd import parallel, pipeline
     from chromosight_amd._lib import get_device
@@ -708,6 +744,8 @@ def time_c5(local_rank, world, dist, torch, steps, warmup):
         table, _w = run()
     sync()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        outputs.update(c5_table=table.select_dtypes("number").to_numpy(dtype=np.float64), c5_windows=np.array(_w, dtype=np.float64))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -727,8 +765,11 @@ def time_c5(local_rank, world, dist, torch, steps, warmup):
 
 
 def run_c5(args, rank, local_rank, world, dist, torch):
-    r = time_c5(local_rank, world, dist, torch, args.steps, args.warmup)
+    outputs = {} if args.dump_outputs else None
+    r = time_c5(local_rank, world, dist, torch, args.steps, args.warmup, outputs)
     if rank == 0:
+        if outputs is not None:
+            r["dumped_outputs"] = dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(dict({"metric": "positions/s quantify end to end (C5: yeast, --inter, 3 x 11x11 borders templates)",
                                "higher_is_better": True, "vs_baseline": None}, **r)))
 
@@ -928,6 +969,7 @@ def main():
     elapsed, kernel_ms = time_steps(dev, wl.step, full_sync, args.steps, args.warmup, dist, local_rank)
     kernel_id = int(dev.lib.cs_last_kernel(dev.ctx))
     elapsed = reduce_max(elapsed)
+    dumped = dump_outputs(args.dump_outputs, wl.outputs()) if args.dump_outputs and rank == 0 else None
 
     # The headline line is complete at this point.  The legs below are reported extras that use more of the stack (the
     # RCCL exchange of the sharded genome has only ever run where several GPUs exist): if one of them hangs, every rank
@@ -949,6 +991,8 @@ def main():
             "roofline_hbm": dict(roof["hbm"], bound="hbm"),
             "kernel_ms": round(kernel_ms, 4),
         }
+        if dumped is not None:
+            head["dumped_outputs"] = dumped
         if world == 1:
             head["gpu_state"] = gpu_state(wl.step, full_sync, CLOCKS_AT_START)
     extras = {}

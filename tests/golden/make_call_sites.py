@@ -1,25 +1,30 @@
 #!/usr/bin/env python3
-"""Which attributes of its detection / preprocessing / stats modules the reference's callers use: data for
-tests/test_integration_recipe.py (authoring container only; /root/reference does not travel).
+"""Which attributes of its detection / preprocessing / stats modules the reference's callers use, and the signatures of
+the functions chromosight_amd.integration rebinds: data for tests/test_integration_recipe.py (needs a checkout of the
+reference; the tests themselves read only the JSON files written here).
 
-    python tests/golden/make_call_sites.py
+    python tests/golden/make_call_sites.py <reference checkout>
 
 Parses chromosight/cli/chromosight.py and chromosight/utils/contacts_map.py with `ast`: `import ... as <alias>` of the
 three modules, then every `<alias>.<attr>` and every `from <module> import <name>`; writes reference_call_sites.json
-{module: {attr: [file:line, ...]}}."""
+{module: {attr: [file:line, ...]}}.  Imports the reference's three modules and writes reference_signatures.json
+{module: {function: [{"name": parameter, "default": value} ...]}} for every function of integration.REBIND: "default" is
+absent for a parameter without one, and a callable default is recorded as {"callable": true}."""
 import ast
+import importlib
+import inspect
 import json
 import pathlib
+import sys
 
-REF = pathlib.Path("/root/reference/chromosight")
-FILES = [REF / "cli" / "chromosight.py", REF / "utils" / "contacts_map.py"]
+HERE = pathlib.Path(__file__).resolve().parent
 MODULES = {"chromosight.utils.detection": "detection", "chromosight.utils.preprocessing": "preprocessing",
            "chromosight.utils.stats": "stats"}
 
 
-def main():
+def call_sites(ref):
     out = {m: {} for m in MODULES.values()}
-    for path in FILES:
+    for path in [ref / "chromosight" / "cli" / "chromosight.py", ref / "chromosight" / "utils" / "contacts_map.py"]:
         tree = ast.parse(path.read_text())
         alias = {}
         rel = f"{path.parent.name}/{path.name}"
@@ -39,11 +44,36 @@ def main():
         for node in ast.walk(tree):
             if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in alias:
                 out[alias[node.value.id]].setdefault(node.attr, []).append(f"{rel}:{node.lineno}")
-    for m in out:
-        out[m] = {k: sorted(set(v)) for k, v in sorted(out[m].items())}
-    dest = pathlib.Path(__file__).with_name("reference_call_sites.json")
-    dest.write_text(json.dumps(out, indent=1) + "\n")
-    print(json.dumps(out, indent=1))
+    return {m: {k: sorted(set(v)) for k, v in sorted(out[m].items())} for m in out}
+
+
+def signatures(ref):
+    sys.path.insert(0, str(HERE.parents[1]))
+    from chromosight_amd import integration
+    sys.path.insert(0, str(ref))
+    out = {}
+    for module, names in integration.REBIND.items():
+        mod = importlib.import_module(f"chromosight.utils.{module}")
+        out[module] = {}
+        for name in names:
+            params = []
+            for p, v in inspect.signature(getattr(mod, name)).parameters.items():
+                entry = {"name": p}
+                if v.default is not inspect.Parameter.empty:
+                    entry["default"] = {"callable": True} if callable(v.default) else v.default
+                params.append(entry)
+            out[module][name] = params
+    return out
+
+
+def main():
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    ref = pathlib.Path(sys.argv[1]).resolve()
+    sites = call_sites(ref)
+    (HERE / "reference_call_sites.json").write_text(json.dumps(sites, indent=1) + "\n")
+    (HERE / "reference_signatures.json").write_text(json.dumps(signatures(ref), indent=1) + "\n")
+    print(json.dumps(sites, indent=1))
 
 
 if __name__ == "__main__":
