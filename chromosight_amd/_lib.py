@@ -127,6 +127,29 @@ class CsFocus(C.Structure):
     ]
 
 
+class CsIceParams(C.Structure):
+    _fields_ = [
+        ("cis_only", C.c_int32),
+        ("ignore_diags", C.c_int32),
+        ("min_nnz", C.c_int32),
+        ("max_iters", C.c_int32),
+        ("min_count", C.c_double),
+        ("mad_max", C.c_double),
+        ("tol", C.c_double),
+        ("rescale_marginals", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class CsIceSpanStats(C.Structure):
+    _fields_ = [
+        ("iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("var", C.c_double),
+        ("scale", C.c_double),
+    ]
+
+
 class CsCall(C.Structure):
     """One entry of a cs_run_calls list (include/chromosight_hip.h)."""
     _fields_ = [
@@ -213,6 +236,8 @@ _PROTOTYPES = {
     "cs_stage_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(CsStageBlock), C.c_int32, C.c_double]),
     "cs_csr_median": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_double)]),
     "cs_csr_median_many": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.c_int32, C.POINTER(C.c_double)]),
+    "cs_ice_balance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32,
+                                 C.POINTER(CsIceParams), C.c_void_p, C.POINTER(CsIceSpanStats)]),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

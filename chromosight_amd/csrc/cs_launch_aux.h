@@ -834,6 +834,41 @@ int launch_peak_rows(const void* src, int src_is_f64, long long ld_src, int rows
 int launch_narrow_rows(const double* src, long long ld_src, float* dst, long long ld_dst, int rows, int cols, int n_cu,
                        hipStream_t stream);
 
+// ---- cs_balance.hip: ICE balancing of the genome pixel table (cs_api_balance.cpp cs_ice_balance) ------------------------
+constexpr int kIceChunk = 64;              // bins per chunk: a chunk never crosses a chromosome
+struct IceChunk {
+    int lo, hi;                            // bins [lo, hi)
+    int span;                              // its span (chromosome with cis_only, else 0)
+    int lim;                               // columns >= lim are dropped (end of the chromosome with cis_only, else n)
+};
+struct IceSpanState {
+    int done, iters, converged, empty;
+    int last_iter, pad;
+    double var, mean;
+};
+struct IceDev {
+    int n, n_chunks, n_spans, ignore_diags;
+    long long nnz;
+    const long long* __restrict__ indptr;  // the pixel table (CSR, upper triangle)
+    const int* __restrict__ indices;
+    long long* colptr;                     // its CSC permutation: n + 1 column offsets, rows, filtered values (csc_val)
+    int* csc_row;
+    const IceChunk* chunks;
+    const int* span_chunk0;                // n_spans + 1 chunk offsets
+    double* bias;                          // n
+    double* marg;                          // n
+    double* marg_nnz;                      // n (initial pass)
+    double* part;                          // 3 per chunk: nonzero count, sum, M2 of its marginals
+    IceSpanState* st;                      // n_spans
+    int* ctl;                              // [0] spans still iterating, [1] last iteration in which a span iterated
+    double tol;
+    int max_iters, rescale;
+};
+size_t ice_sort_scratch_bytes(long long nnz, int end_bit);
+int ice_prepare(const IceDev& D, const void* data, int data_is_f64, void* csc_val, const int* bin_lim, int* rowid, int* iota,
+                int* col_sorted, int* perm, void* sort_tmp, size_t sort_bytes, int end_bit, int* bad, int n_cu, hipStream_t stream);
+int ice_iterate(const IceDev& D, const void* data, int data_is_f64, const void* csc_val, int max_iters, hipStream_t stream);
+
 // median of the stored values of a view (cs_foci.hip)
 int csr_median(const CsrView& M, int n_cu, hipStream_t stream, void* (*grow)(void*, size_t), void* user, double* h_median);
 int csr_median_many(const CsrView* views, int n, int n_cu, hipStream_t stream, void* (*grow)(void*, size_t), void* user, double* h_medians);

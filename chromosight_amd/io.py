@@ -72,6 +72,8 @@ def _attr_int(tool, path, group, name):
 def _weights(uri, balance, norm, n_bins, read):
     """The balancing weights under the rules of load_cool; read() returns the column or None when it is absent."""
     weight = read()
+    if norm is None:                      # _read_cool: the column as stored, None when the file has none
+        return None if weight is None else np.asarray(weight, dtype=np.float64)
     if weight is not None:
         weight = np.asarray(weight, dtype=np.float64)
         return np.where(np.isfinite(weight), 1.0, np.nan) if norm == "raw" else weight
@@ -151,6 +153,16 @@ def load_cool(uri, balance="weight", norm="auto"):
     column (h5dump failure, unsupported type) propagate."""
     if norm not in ("auto", "raw"):
         raise ValueError("norm must be one of: auto, raw ('force' re-balances the file: not part of this package)")
+    return _load(uri, balance, norm)
+
+
+def _read_cool(uri, balance="weight"):
+    """The dictionary of load_cool with the `bins/<balance>` column exactly as stored, or weight None when the file has no
+    such column (pipeline.open_cool balances it on the device).  Never writes to the file."""
+    return _load(uri, balance, None)
+
+
+def _load(uri, balance, norm):
     path, _, group = str(uri).partition("::")
     group = "/" + group.strip("/") if group else ""
     cool = None

@@ -322,7 +322,9 @@ class DeviceCool:
         if b1.size and not (np.all(b1[1:] >= b1[:-1]) and np.all((b1[1:] > b1[:-1]) | (b2[1:] > b2[:-1]))):
             order = np.lexsort((b2, b1))                      # unsorted / duplicated pixel table
             b1, b2, cnt = b1[order], b2[order], cnt[order]
-        weight = np.asarray(cool["weight"], dtype=np.float64)
+        # no "weight" (or None): a table without balancing weights -- nothing is staged from it until set_weights()
+        # (pipeline.open_cool balances it on the device: chromosight_amd/balance.py)
+        weight = cool.get("weight") if hasattr(cool, "get") else cool["weight"]
         indptr = np.searchsorted(b1, np.arange(n_bins + 1)).astype(np.int64)
         # integer counts below 2^24 are exact in float32 (half the bytes of every pass)
         small = cnt.size == 0 or (np.issubdtype(cnt.dtype, np.integer) and cnt.max() < (1 << 24)) or \
@@ -330,19 +332,19 @@ class DeviceCool:
         self.val_dtype = np.float32 if small else np.float64
         # ... and, when none is negative, can be staged as a band of raw counts that its readers detrend (CS_LAYOUT_BAND_COUNTS)
         # (and no weight: the readers' NaN -> 0 is a max with 0)
-        self.counts_ok = bool(small and (cnt.size == 0 or cnt.min() >= 0) and not np.any(weight < 0))
+        self._counts_exact = bool(small and (cnt.size == 0 or cnt.min() >= 0))
         self.nnz = int(b1.size)
         self.indptr = dev.to_device(indptr, np.int64)
         self.indices = dev.to_device(b2, np.int32)
         self.data = dev.to_device(cnt, self.val_dtype)
-        self.weight = dev.to_device(weight, np.float64)
-        miss = ~np.isfinite(weight)
-        self.miss_host = miss
-        self.miss = dev.to_device(miss.astype(np.uint8))
-        self.det = dev.to_device((~miss).astype(np.uint8))
         self.host = {"binsize": self.binsize, "chrom_offset": off, "chrom_names": np.asarray(self.names), "bin1_id": b1,
-                     "bin2_id": b2, "count": cnt, "weight": weight, "bin_start": self.bin_start, "bin_end": self.bin_end}
-        self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes + self.weight.nbytes
+                     "bin2_id": b2, "count": cnt, "weight": None, "bin_start": self.bin_start, "bin_end": self.bin_end}
+        self._retired = []
+        self.weight = self.miss = self.det = self.miss_host = None
+        self.counts_ok = False
+        self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes
+        if weight is not None:
+            self.set_weights(weight)
         # what cs_stage_blocks needs: every stored pixel on or above the diagonal (a .cool's symmetric-upper storage)
         self.upper = bool(b1.size == 0 or np.all(b2 >= b1))
         self._band = _Scratch(dev)
@@ -350,6 +352,39 @@ class DeviceCool:
         self._stage_lock = threading.RLock()
         self._free = _FreeList()        # HBM of released resident blocks, reused by the next staging
         self._workers = None
+
+    def set_weights(self, weight):
+        """Take new balancing weights (n_bins values, NaN = bin without a weight): uploads `weight` and the missing /
+        detectable flags, refreshes counts_ok and the host copy.  The pixel table stays as it is.  The buffers of the
+        previous weights are kept alive (blocks staged before point into them); stage again to use the new ones."""
+        weight = np.asarray(weight, dtype=np.float64)
+        if weight.shape != (self.n_bins,):
+            raise ValueError(f"weights of shape {weight.shape} for a table of {self.n_bins} bins")
+        if self.weight is not None:
+            self._retired.append((self.weight, self.miss, self.det))
+        dev = self.dev
+        self.counts_ok = bool(self._counts_exact and not np.any(weight < 0))
+        self.weight = dev.to_device(weight, np.float64)
+        miss = ~np.isfinite(weight)
+        self.miss_host = miss
+        self.miss = dev.to_device(miss.astype(np.uint8))
+        self.det = dev.to_device((~miss).astype(np.uint8))
+        self.host["weight"] = weight
+        self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes + self.weight.nbytes
+
+    @property
+    def has_weights(self):
+        return self.weight is not None
+
+    def _need_weights(self):
+        if self.weight is None:
+            raise ValueError("this pixel table has no balancing weights: balance it first (pipeline.open_cool, "
+                             "balance.ice_balance + DeviceCool.set_weights)")
+
+    def csr(self):
+        """The whole-genome pixel table as a plain cs_csr (no weights)."""
+        return CsCsr(self.n_bins, self.n_bins, self.nnz, self.indptr.ptr, self.indices.ptr, self.data.ptr,
+                     np_dtype_code(self.val_dtype), 0, None, None, None)
 
     def _resident(self, nbytes, dev=None):
         buf = self._free.take(nbytes)
@@ -360,6 +395,7 @@ class DeviceCool:
         (below).  workers > 1: host threads with their own contexts stage several blocks at a time (see _Workers) --
         measured slower than ONE stream on the 23-block genome (the hand-over costs two synchronisations per block).
         Every block's staging is complete on return."""
+        self._need_weights()
         chroms = list(chroms)
         lazy64 = options.pop("lazy64", False)                # (only the one-call staging knows lazily evaluated bands)
         counts = options.pop("counts", None)                 # (... and bands of raw counts)
@@ -522,6 +558,7 @@ class DeviceCool:
         kept (preprocessing.py:173-188, without --smooth-trend), so the detrended values are the same numbers, and a band
         view with fewer stored diagonals reads every pixel beyond them as 0 (diag_trim).  None when a view cannot stand in
         (dense-staged short chromosomes, row windows, a longer distance than the block holds)."""
+        self._need_weights()
         n = block.shape[0]
         keep = min(max_dist, n) + largest_kernel
         if (block.inter or block.sig.layout not in (LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW)
@@ -569,10 +606,12 @@ class DeviceCool:
 
     def stage_intra(self, *args, dev=None, **options):
         """_stage_intra holding the context it uses (one call in flight per context: engine._one_call_per_context)."""
+        self._need_weights()
         with (dev or self.dev).lock:
             return self._stage_intra(*args, dev=dev, **options)
 
     def stage_inter(self, *args, **options):
+        self._need_weights()
         with self.dev.lock:
             return self._stage_inter(*args, **options)
 
@@ -685,6 +724,7 @@ class DeviceCool:
     def stage_inter_many(self, pairs, dtype=np.float64, stream=None):
         """stage_inter(resident=True) for SEVERAL inter-chromosomal blocks: the extents of all of them, then their medians with
         one native call (cs_csr_median_many: two synchronisations in all instead of two per block), then the dense maps."""
+        self._need_weights()
         pairs = list(pairs)
         if not pairs:
             return []
@@ -779,6 +819,7 @@ class DeviceCool:
         return np.where(ok, self.offsets[np.maximum(ci, 0)] + local, -1)
 
     def block_bins(self, ci):
+        self._need_weights()
         s, e = int(self.offsets[ci]), int(self.offsets[ci + 1])
         return np.flatnonzero(~self.miss_host[s:e])
 
@@ -942,6 +983,36 @@ def with_win_size(kernel_config, win_size):
 def sub_matrices(dcool, inter):
     """(chrom a, chrom b) of every sub-matrix in the reference's order (contacts_map.py:274-312)."""
     return [(a, b) for a in range(dcool.n_chrom) for b in range(dcool.n_chrom) if a == b or (a < b and inter)]
+
+
+def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None):
+    """A .cool (path, `file.mcool::/resolutions/<binsize>`, or a decoded dictionary) resident on the device with the
+    weights the reference's HicGenome.normalize gives it (contacts_map.py:182-229):
+
+    - norm="auto": the stored `bins/<balance>` column when the file has one, else ICE on the device;
+    - norm="force": ICE on the device even when the file has weights;
+    - norm="raw": raw counts; the detectable bins are those of the stored weights, or of ICE when there are none
+      (weights 1.0 on them, NaN elsewhere).
+
+    ICE runs with the reference's arguments (cooler.balance_cooler: cis_only = not inter, mad_max = n_mads, ignore_diags=2,
+    min_nnz=10, max_iters=200; chromosight_amd/balance.py).  Unlike the reference, the new weights are NOT written back
+    into the input file.  The result goes to detect / quantify / detect_to_files and the parallel drivers."""
+    if norm not in ("auto", "raw", "force"):
+        raise ValueError("norm must be one of: auto, raw, force")
+    if isinstance(uri_or_cool, (str, bytes)) or hasattr(uri_or_cool, "__fspath__"):
+        from . import io as cio
+        cool = cio._read_cool(uri_or_cool, balance)
+    else:
+        cool = dict(uri_or_cool)
+    weight = None if norm == "force" else cool.get("weight")
+    raw = (lambda w: np.where(np.isfinite(np.asarray(w, dtype=np.float64)), 1.0, np.nan)) if norm == "raw" else (lambda w: w)
+    cool["weight"] = None if weight is None else raw(weight)
+    dcool = DeviceCool(cool, dev)
+    if weight is None:
+        from .balance import ice_balance
+        weight, _ = ice_balance(dcool, cis_only=not inter, mad_max=n_mads, ignore_diags=2, min_nnz=10, max_iters=200)
+        dcool.set_weights(raw(weight))
+    return dcool
 
 
 def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, inter=False, subsample=None, seed=0,

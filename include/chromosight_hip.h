@@ -342,6 +342,35 @@ int cs_csr_median(cs_ctx* ctx, void* stream, const cs_csr* mat, double* h_median
  * task per sub-matrix).  h_medians[i] = NaN for an empty view.  Synchronous. */
 int cs_csr_median_many(cs_ctx* ctx, void* stream, const cs_csr* mats, int32_t n, double* h_medians);
 
+/* ---- ICE balancing of the whole-genome pixel table (cooler.balance_cooler, what the reference's HicGenome.normalize
+ * runs on a file without weights: contacts_map.py:203-221) ---- */
+typedef struct {
+    int32_t cis_only;          /* 1: every chromosome balanced on its own cis pixels; 0: one genome-wide span, trans included */
+    int32_t ignore_diags;      /* pixels with bin2 - bin1 < ignore_diags are dropped */
+    int32_t min_nnz;           /* bins with fewer nonzero filtered pixels get weight NaN (0: off) */
+    int32_t max_iters;         /* >= 1 */
+    double min_count;          /* bins whose filtered marginal is below it get weight NaN (0: off) */
+    double mad_max;            /* MAD filter on the log marginals, each chromosome scaled by its median first (0: off) */
+    double tol;                /* a span stops when the variance of its nonzero marginals is below it (> 0) */
+    int32_t rescale_marginals; /* 1: weights divided by sqrt(scale) of their span (marginals of the balanced table ~ 1) */
+    int32_t reserved;          /* 0 */
+} cs_ice_params;
+typedef struct {
+    int32_t iterations;        /* marginal passes of the span */
+    int32_t converged;         /* 0: max_iters reached with var >= tol (cooler warns: ConvergenceWarning) */
+    double var;                /* variance of the nonzero marginals of the last pass (0 for a span without any) */
+    double scale;              /* their mean (NaN for a span without any: its weights are all NaN) */
+} cs_ice_span_stats;
+/* ICE weights of `genome` -- the resident upper-triangle pixel table (square, plain row pointers, no weights, every stored
+ * pixel on or above the diagonal, nnz < 2^31) -- into d_bias (n_rows doubles, NaN = bin without a weight).  chrom_offsets:
+ * n_chrom + 1 host values from 0 to n_rows.  h_stats: one entry per span (n_chrom with cis_only, else 1).  The column side of
+ * the marginals comes from a CSC permutation of the table built on the device for the call; every sum is a fixed-order
+ * float64 reduction (no float atomics): the weights are bitwise identical from call to call.  Iterations are queued with a
+ * device-side "every span converged" word; two host synchronisations per call (the filter medians on the host, the
+ * statistics).  Synchronous.  The table is never written. */
+int cs_ice_balance(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t* chrom_offsets, int32_t n_chrom,
+                   const cs_ice_params* params, double* d_bias, cs_ice_span_stats* h_stats);
+
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
     double pearson;         /* candidate threshold: coefficient >= pearson and != 0 (detection.py:417-421) */
