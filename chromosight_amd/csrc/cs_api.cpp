@@ -666,10 +666,10 @@ int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, 
             if (rc != CS_OK) return rc;
             int path = 0;
             rc = cs::launch_corr_mfma_f32(A, E, stream, &path);
-            ctx->last_kernel = path == 2 ? CS_KERNEL_MFMA_REG : CS_KERNEL_MFMA;
+            ctx->last_kernel = path == 3 ? CS_KERNEL_MFMA_LIST : path == 2 ? CS_KERNEL_MFMA_REG : CS_KERNEL_MFMA;
             if (rc == -5) return CS_NEED_MAP;
             if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-            if (path == 2 && A.cand_keys) ctx->cand_fused = true;
+            if ((path == 2 || path == 3) && A.cand_keys) ctx->cand_fused = true;
             return CS_OK;
         }
     }
@@ -710,7 +710,7 @@ int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, 
         if (rc != CS_OK) return rc;
         int dense_path = 0;
         rc = cs::launch_corr_mfma_f32(A, E, stream, &dense_path);
-        ctx->last_kernel = dense_path == 1 ? CS_KERNEL_MFMA_DENSE : dense_path == 2 ? CS_KERNEL_MFMA_REG : CS_KERNEL_MFMA;
+        ctx->last_kernel = dense_path == 1 ? CS_KERNEL_MFMA_DENSE : dense_path == 2 ? CS_KERNEL_MFMA_REG : dense_path == 3 ? CS_KERNEL_MFMA_LIST : CS_KERNEL_MFMA;
     } else if (allow_fast && fast_compatible(A) && fast_available(A.km, A.kn, &K) && !std::getenv("CHROMOSIGHT_HIP_WIDE_ALL")) {
         ctx->last_kernel = CS_KERNEL_STREAM;
 #ifdef CS_HAVE_FAST

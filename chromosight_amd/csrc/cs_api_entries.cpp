@@ -602,6 +602,36 @@ int cs_accept_records(const cs_focus* h_rec, int64_t n_blocks, const int64_t* h_
 }
 
 
+int cs_csr_tile_occupancy(cs_ctx* ctx, void* stream_, const cs_csr* mat, int32_t row_off, int32_t km, int32_t kn, int32_t row_begin,
+                          int32_t row_end, int32_t* d_tiles, int64_t cap, int64_t* n_tiles)
+{
+    CS_ENTER(ctx);
+    cs::CsrView v;
+    int rc = csr_view(ctx, mat, &v);
+    if (rc) return rc;
+    if (!n_tiles || cap < 0 || (cap > 0 && !d_tiles)) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
+    if (km <= 0 || kn <= 0 || !(km & 1) || !(kn & 1) || km > 65 || kn > 65) return fail(ctx, CS_ERR_INVALID, "bad template shape");
+    if (row_begin < 0 || row_end < row_begin || v.n_cols <= 0) return fail(ctx, CS_ERR_INVALID, "bad tile grid");
+    *n_tiles = 0;
+    const long long n = ((long long)v.n_cols + 63) / 64 * (((long long)row_end - row_begin + 63) / 64);
+    if (n > 0x7fffffffLL) return fail(ctx, CS_ERR_OVERFLOW, "%lld tiles", n);
+    if (n == 0) return CS_OK;
+    const size_t off_cnt = ((size_t)(n + 31) / 32 * 4 + 255) & ~(size_t)255;
+    rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, off_cnt + 256);
+    if (rc) return rc;
+    if (!ctx->h_counts) CS_HIP(ctx, hipHostMalloc((void**)&ctx->h_counts, 64, hipHostMallocDefault));
+    char* pool = (char*)ctx->d_pool;
+    hipStream_t stream = (hipStream_t)stream_;
+    rc = cs::launch_tile_occupancy(v, row_off, km, kn, row_begin, row_end, (unsigned*)pool, d_tiles, cap, (long long*)(pool + off_cnt),
+                                   ctx->n_cu, stream);
+    if (rc) return fail(ctx, CS_ERR_HIP, "occupancy launch failed: %s", hipGetErrorString((hipError_t)rc));
+    CS_HIP(ctx, hipMemcpyAsync(ctx->h_counts + 3, pool + off_cnt, 8, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipStreamSynchronize(stream));
+    *n_tiles = ctx->h_counts[3];
+    if (*n_tiles > cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld tiles, room for %lld", (long long)*n_tiles, (long long)cap);
+    return CS_OK;
+}
+
 int cs_csr_median(cs_ctx* ctx, void* stream_, const cs_csr* mat, double* h_median)
 {
     CS_ENTER(ctx);

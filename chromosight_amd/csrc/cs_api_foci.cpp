@@ -59,6 +59,8 @@ int corr_candidates_f32(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal
         A.cand_dhi = sink->hi_diag;
         A.defer_args = sink->defer_args;
         A.defer_rsym = sink->defer_rsym;
+        A.cand_tiles = ctx->cand_tiles;
+        A.cand_n_tiles = ctx->cand_n_tiles;
     } else if (!out || !out->d_ptr) {
         return fail(ctx, CS_ERR_INVALID, "candidate mode needs a sink or a map");
     }
@@ -1127,6 +1129,55 @@ int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
         CS_HIP(ctx, hipMemcpyAsync(h_vals, d_vals, 8 * (size_t)n, hipMemcpyDeviceToHost, stream));
         CS_HIP(ctx, hipStreamSynchronize(stream));
     }
+    return CS_OK;
+}
+
+int cs_candidates_tiles(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_kernel* kernel,
+                        const cs_normxcorr2_params* p, const cs_foci_params* fp, const int32_t* d_tiles, int32_t n_tiles,
+                        int32_t* h_rows, int32_t* h_cols, double* h_vals, int64_t cap, int64_t* n_out)
+{
+    CS_ENTER(ctx);
+    if (!signal || !kernel || !p || !fp) return fail(ctx, CS_ERR_INVALID, "null argument");
+    if (!n_out || cap < 0 || (cap > 0 && (!h_rows || !h_cols || !h_vals))) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
+    if (n_tiles < 0 || (n_tiles > 0 && !d_tiles)) return fail(ctx, CS_ERR_INVALID, "bad tile list");
+    if (signal->layout != CS_LAYOUT_DENSE) return fail(ctx, CS_ERR_UNSUPPORTED, "a tile list needs a dense signal (the 64 x 64 grid of a dense map)");
+    *n_out = 0;
+    int rb = 0, re = p->ms;
+    if (p->row_end > p->row_begin) {
+        if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
+        rb = p->row_begin;
+        re = p->row_end;
+    }
+    const long long tiles_x = ((long long)p->ns + 63) / 64, tiles_y = ((long long)(re - rb) + 63) / 64;
+    if (n_tiles == 0) return CS_OK;                 // no tile a stored pixel reaches: no candidate
+    // the list on the host: checked (the list instance of the tile kernel indexes its grid with it) and, for the kernels that
+    // compute every tile (no list instance: non-square templates, maps), the filter of their candidates
+    std::vector<int32_t> tiles((size_t)n_tiles);
+    hipStream_t stream = (hipStream_t)stream_;
+    CS_HIP(ctx, hipMemcpyAsync(tiles.data(), d_tiles, 4 * (size_t)n_tiles, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipStreamSynchronize(stream));
+    std::vector<uint8_t> listed((size_t)(tiles_x * tiles_y), 0);
+    for (int32_t t = 0; t < n_tiles; ++t) {
+        if (tiles[(size_t)t] < 0 || tiles[(size_t)t] >= tiles_x * tiles_y)
+            return fail(ctx, CS_ERR_INVALID, "tile %d of the list (%d) outside the %lld x %lld grid", t, tiles[(size_t)t], tiles_y, tiles_x);
+        listed[(size_t)tiles[(size_t)t]] = 1;
+    }
+    ctx->cand_tiles = d_tiles;
+    ctx->cand_n_tiles = n_tiles;
+    int rc = cs_candidates(ctx, stream_, signal, kernel, p, fp, h_rows, h_cols, h_vals, cap, n_out);
+    ctx->cand_tiles = nullptr;
+    ctx->cand_n_tiles = 0;
+    if (rc) return rc;
+    int64_t k = 0;
+    for (int64_t t = 0; t < *n_out; ++t) {
+        const long long tile = (long long)((h_rows[t] - rb) / 64) * tiles_x + h_cols[t] / 64;
+        if (!listed[(size_t)tile]) continue;
+        h_rows[k] = h_rows[t];
+        h_cols[k] = h_cols[t];
+        h_vals[k] = h_vals[t];
+        ++k;
+    }
+    *n_out = k;
     return CS_OK;
 }
 

@@ -661,9 +661,27 @@ __device__ __forceinline__ void rim_correction(const float* __restrict__ T, int 
 template <bool VEC4, bool REG, bool RSYM = false, bool CAND = false>
 __global__ __launch_bounds__(256, 2) void corr_mfma_dense_kernel(const MfmaDenseArgs A)
 {
-    constexpr bool TABLE = false;
+    constexpr bool TABLE = false, LIST = false;
     constexpr unsigned long long table_entry = 0;
     constexpr int table_tile = 0, table_tile_end = 0, table_tile_step = 0;
+    const int* const tile_list = nullptr;
+    (void)table_entry; (void)table_tile; (void)table_tile_end; (void)table_tile_step; (void)tile_list;
+#define MFD_NOMASK_KS A.ks
+#include "cs_corr_mfma_body.inc"
+#undef MFD_NOMASK_KS
+}
+
+// The masked candidate instance on a LIST of tiles (cs_candidates_tiles): A.n_tiles entries of `tiles`, each a tile index
+// by * tiles_x + bx of the dense output grid, in place of the whole grid -- tiles whose windows hold no stored pixel are not
+// visited (their coefficients are all 0, never a candidate).  Everything else is corr_mfma_dense_kernel<true, true, RSYM, true>.
+template <bool RSYM>
+__global__ __launch_bounds__(256, 2) void corr_mfma_list_kernel(const MfmaDenseArgs A, const int* __restrict__ tiles)
+{
+    constexpr bool VEC4 = true, REG = true, CAND = true;
+    constexpr bool TABLE = false, LIST = true;
+    constexpr unsigned long long table_entry = 0;
+    constexpr int table_tile = 0, table_tile_end = 0, table_tile_step = 0;
+    const int* const tile_list = tiles;
     (void)table_entry; (void)table_tile; (void)table_tile_end; (void)table_tile_step;
 #define MFD_NOMASK_KS A.ks
 #include "cs_corr_mfma_body.inc"
@@ -688,7 +706,9 @@ template <bool VEC4, bool REG, bool RSYM, bool CAND, bool TABLE_ = true>
 __device__ __forceinline__ void mfma_dense_tiles_table(MfmaDenseArgsC& A, const unsigned long long table_entry, const int table_tile,
                                                        const int table_tile_end, const int table_tile_step)
 {
-    constexpr bool TABLE = TABLE_;
+    constexpr bool TABLE = TABLE_, LIST = false;
+    const int* const tile_list = nullptr;
+    (void)tile_list;
     const KernelStats<float> no_ks{};       // (the unmasked epilogue is never part of a table instance: REG)
 #define MFD_NOMASK_KS no_ks
 #include "cs_corr_mfma_body.inc"
@@ -904,6 +924,21 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
                 std::memcpy(A.defer_args, &D, sizeof(D));
                 if (A.defer_rsym) *A.defer_rsym = rsym ? 1 : 0;
                 return 0;
+            }
+            if (A.cand_tiles) {
+                // a tile list (cs_candidates_tiles, dense outputs only): the list instance walks its A.cand_n_tiles entries
+                if (!cand || D.band_out || D.by_cut != A.tiles_y) return -5;
+                *dense_path = 3;
+                D.n_tiles = A.cand_n_tiles;
+                if (D.n_tiles <= 0) return 0;
+                typedef void (*list_kernel_t)(const MfmaDenseArgs, const int*);
+                const list_kernel_t kl = rsym ? corr_mfma_list_kernel<true> : corr_mfma_list_kernel<false>;
+                hipError_t el = allow_big_lds((const void*)kl);
+                if (el != hipSuccess) return (int)el;
+                int grid_l = (int)std::min<long long>(D.n_tiles, 2LL * A.n_cu);
+                if (A.grid_cap > 0 && grid_l > A.grid_cap) grid_l = std::max(8, A.grid_cap & ~7);
+                hipLaunchKernelGGL(kl, dim3((unsigned)grid_l), dim3(256), MFD_SMEM_REG + MFD_LAUNCH_EXTRA, stream, D, A.cand_tiles);
+                return (int)hipGetLastError();
             }
             typedef void (*reg_kernel_t)(const MfmaDenseArgs);
             const reg_kernel_t kr = rsym ? (cand ? corr_mfma_dense_kernel<true, true, true, true> : corr_mfma_dense_kernel<true, true, true, false>)

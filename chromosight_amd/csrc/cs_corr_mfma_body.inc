@@ -1,6 +1,7 @@
 // Body of corr_mfma_dense_kernel and of the table instance behind corr_mfma_blocks_kernel (cs_corr_mfma.hip includes this
 // file twice).  In scope: the template parameters VEC4, REG, RSYM, CAND; `A` (the argument block); constexpr bool TABLE and,
-// when it is set, table_entry (address of the block's entry), table_tile, table_tile_end, table_tile_step; the macro
+// when it is set, table_entry (address of the block's entry), table_tile, table_tile_end, table_tile_step; constexpr bool LIST
+// and tile_list (LIST: the workgroups walk a list of tile indices by * tiles_x + bx, A.n_tiles long, instead of every tile); the macro
 // MFD_NOMASK_KS (the statistics block as the unmasked epilogue passes it on: A.ks).  Textual
 // inclusion, not a function call: the masked instances sit at 256 registers and their allocation follows the exact
 // statement order (a call boundary cost 3 % on C4').
@@ -71,6 +72,7 @@
     }
 
     auto tile_origin = [&](int tile, int& I0, int& J0) {
+        if constexpr (LIST) tile = tile_list[tile];       // (cs_candidates_tiles: only the tiles a stored pixel reaches)
         int by = tile / A.tiles_x;
         int bx = tile - by * A.tiles_x;
         if constexpr (REG) {

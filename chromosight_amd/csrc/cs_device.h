@@ -232,6 +232,10 @@ struct CorrArgs {
     void* defer_args;
     int* defer_rsym;
     int cand_dlo, cand_dhi;  // only pixels on these diagonals are candidates (diag_trim of the coefficient map)
+    // non-null (candidate sink, masked tile kernel, dense output): the device list of the cand_n_tiles output tiles to visit
+    // (by * tiles_x + bx, cs_candidates_tiles); the other kernels compute every tile and the entry filters their candidates
+    const int* cand_tiles;
+    int cand_n_tiles;
     int fix_on, fix_hi_w, fix_hi_d0;
     const TC* rowtab;
     const TC* coltab;

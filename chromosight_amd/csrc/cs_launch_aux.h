@@ -826,6 +826,11 @@ int launch_rescore_f64_keys(const CorrArgs<double>& A, const long long* keys, in
                             double* out_corr, const long long* n_ptr, long long* count_copy, long long* zero_next, hipStream_t stream);
 int launch_csr_band_extent(const CsrView& M, int lo_diag, int hi_diag, long long* begin, long long* end,
                            hipStream_t stream);
+// cs_occupancy.hip: the output tiles (64 x 64, tile row ty from row_begin + 64 ty) of a dense map whose windows of a km x kn
+// template reach a stored pixel with count > 0 and finite weights of the view (view row r = block row row_off + r): `bits`
+// (ceil(tiles / 32) words, cleared here) -> out[] in increasing order (at most cap written), *d_count = their number
+int launch_tile_occupancy(const CsrView& M, int row_off, int km, int kn, int row_begin, int row_end, unsigned* bits, int* out,
+                          long long cap, long long* d_count, int n_cu, hipStream_t stream);
 int launch_law_finish(const double* sum, const long long* cnt, int n, double* law, hipStream_t stream);
 // largest |pixel| of rows x cols values (as the bits of a float: a NaN or an infinity compares above every finite value),
 // combined into *d_peak_bits with an atomic maximum (zero it first)

@@ -411,6 +411,49 @@ def run_candidates(dev, sig, shape, kspec, row_window, *, pearson, lo_diag, hi_d
 
 
 @_one_call_per_context
+def run_tile_occupancy(dev, view, row_off, km, kn, row_window, ns, stream=None):
+    """Which 64 x 64 output tiles of the rows row_window = (a, b) of a dense map (ns columns) can hold a candidate of a
+    km x kn template (cs_csr_tile_occupancy): those whose windows reach a pixel of the CSR view `view` (its row r is row
+    row_off + r of the map) with count > 0 and finite weights.  Returns (device buffer of int32 tile indices
+    ty * ceil(ns / 64) + tx in increasing order, their number)."""
+    a, b = int(row_window[0]), int(row_window[1])
+    cap = max(1, (int(ns) + 63) // 64 * ((b - a + 63) // 64))
+    tiles = dev.empty(cap, np.int32)
+    n = C.c_int64(0)
+    dev._check(dev.lib.cs_csr_tile_occupancy(dev.ctx, stream, C.byref(view), int(row_off), int(km), int(kn), a, b, tiles.ptr, cap,
+                                             C.byref(n)))
+    return tiles, int(n.value)
+
+
+@_one_call_per_context
+def run_candidates_tiles(dev, sig, shape, kspec, row_window, tiles, n_tiles, *, pearson, lo_diag, hi_diag, inter, full, sym_upper,
+                         max_dist, mask_mode=MASK_NONE, miss_row=None, miss_col=None, missing_tol=0.75, precision=None, stream=None,
+                         **_unused):
+    """run_candidates on the tiles of a device list only (cs_candidates_tiles; `tiles`: anything with .ptr, n_tiles int32 tile
+    indices of the dense grid of row_window -- what run_tile_occupancy returns)."""
+    if float(pearson) <= LOW_PEARSON_F64:
+        precision = "f64"
+    params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, None, missing_tol,
+                          compute_code(precision), row_window)
+    fp = CsFociParams(float(pearson), rescore_margin(pearson), 1, 0, int(lo_diag), int(hi_diag), int(bool(inter)), 0)
+    cap = 1 << 14
+    while True:
+        rows, cols = np.empty(cap, np.int32), np.empty(cap, np.int32)
+        vals = np.empty(cap, np.float64)
+        n = C.c_int64(0)
+        rc = dev.lib.cs_candidates_tiles(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp),
+                                         tiles.ptr if n_tiles else None, int(n_tiles), rows.ctypes.data, cols.ctypes.data,
+                                         vals.ctypes.data, cap, C.byref(n))
+        if rc == -4 and n.value > cap:
+            cap = int(n.value) + int(n.value) // 4
+            continue
+        dev._check(rc)
+        break
+    k = int(n.value)
+    return rows[:k], cols[:k], vals[:k]
+
+
+@_one_call_per_context
 def run_label_foci(dev, shape, rows, cols, vals, *, min_size=2, diag_only=False, stream=None):
     """Second half of detect mode (cs_label_foci): the 4-connected foci of a candidate list -- the
     coordinates of each focus at its maximum and its size, in the order of cs_detect_foci."""

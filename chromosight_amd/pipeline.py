@@ -20,8 +20,8 @@ import pandas as pd
 import scipy.sparse as sp
 
 from . import engine
-from ._lib import (COUNTS_HEADER_BYTES, CS_F32, CS_F64, LAYOUT_BAND, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED,
-                   LAYOUT_DENSE, LAZY_BAND_BYTES, CsCsr, CsMatrix, CsStageBlock,
+from ._lib import (COUNTS_HEADER_BYTES, CS_F32, CS_F64, FOCUS_DTYPE, LAYOUT_BAND, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW, LAYOUT_BAND_LAZY,
+                   LAYOUT_BAND_PADDED, LAYOUT_DENSE, LAZY_BAND_BYTES, MASK_BINS, CsCsr, CsMatrix, CsStageBlock,
                    get_device, np_dtype_code)
 from .utils import detection as cid
 from .utils import preprocessing as preproc
@@ -291,6 +291,64 @@ class _Workers:
 
     def map(self, fn, items):
         return list(self.pool.map(fn, items))
+
+
+# Trans blocks in row strips (detect / quantify with inter=True): the dense float64 staging of ONE strip stays below this many
+# bytes unless the caller passes inter_budget.  8 GiB beside a resident genome: the float32 copy the tile
+# kernel reads (context scratch) adds half of it.
+INTER_BUDGET_DEFAULT = 8 << 30
+_MAX_STRIP_ELEMENTS = (1 << 31) - 1
+
+
+def _inter_ld(n_c):
+    return (int(n_c) + 15) // 16 * 16             # (the row pitch of _stage_inter)
+
+
+def plan_inter_strips(n_r, n_c, budget, halo, esz=8):
+    """Row strips (a, b) of an n_r x n_c trans block whose dense staging -- rows a - halo .. b + halo - 1 clipped to the block,
+    `esz`-byte values at the pitch of _stage_inter -- stays within `budget` bytes and below 2^31 elements.  Every row is owned
+    by exactly one strip; the strips are as even as the budget allows.  One strip (0, n_r) when the whole block fits."""
+    if budget is None or not budget > 0:
+        raise ValueError("inter_budget must be a positive number of bytes")
+    n_r, n_c, halo = int(n_r), int(n_c), int(halo)
+    ld = _inter_ld(n_c)
+    max_rows = min(int(budget) // (ld * esz), _MAX_STRIP_ELEMENTS // ld)
+    if n_r <= max_rows:
+        return [(0, n_r)]
+    own = max_rows - 2 * halo
+    if own < 1:
+        raise ValueError(f"inter_budget of {int(budget)} bytes cannot hold one row and its halo of {halo} rows "
+                         f"({(1 + 2 * halo) * ld * esz} bytes) of a block of {n_c} columns")
+    n_strips = -(-n_r // own)
+    per = -(-n_r // n_strips)
+    return [(a, min(n_r, a + per)) for a in range(0, n_r, per)]
+
+
+def _strip_rows(n_r, rows, halo):
+    return max(0, rows[0] - halo), min(n_r, rows[1] + halo)
+
+
+class _StripPool:
+    """The device buffer of the row strips of trans blocks, staged one at a time: reused while it is large enough, freed before
+    a larger one is allocated.  high_water: the largest number of bytes it held."""
+
+    def __init__(self, dev):
+        self.dev, self.buf, self.high_water = dev, None, 0
+
+    def take(self, nbytes):
+        nbytes = max(int(nbytes), 1)
+        if self.buf is None or self.buf.nbytes < nbytes:
+            if self.buf is not None:
+                self.dev.sync()
+                self.buf = None
+            self.buf = self.dev.empty(nbytes, np.uint8)
+            self.high_water = max(self.high_water, self.buf.nbytes)
+        return self.buf
+
+    def release(self):
+        if self.buf is not None:
+            self.dev.sync()
+            self.buf = None
 
 
 _WORKER_POOLS = {}
@@ -610,10 +668,87 @@ class DeviceCool:
         with (dev or self.dev).lock:
             return self._stage_intra(*args, dev=dev, **options)
 
-    def stage_inter(self, *args, **options):
+    def stage_inter(self, *args, rows=None, largest_kernel=None, median=None, **options):
+        """_stage_inter; rows = (a, b): only the rows a <= i < b of the block plus a halo of (largest_kernel - 1) // 2 rows on
+        either side, dense, CsMatrix.row0 = a - halo (clipped to the block), in the strip pool (inter_high_water) -- the block
+        scaled by the median of the WHOLE block (`median`, else computed here: inter_median), so a strip holds the same values
+        as those rows of the unsplit block.  The strip's `view` (cs_csr of its staged rows) is valid until the next staging."""
         self._need_weights()
         with self.dev.lock:
-            return self._stage_inter(*args, **options)
+            if rows is None:
+                return self._stage_inter(*args, **options)
+            return self._stage_inter_rows(*args, rows=rows, largest_kernel=largest_kernel, median=median, **options)
+
+    @property
+    def inter_high_water(self):
+        """Largest number of device bytes the strip pool of trans blocks held (stage_inter(rows=...))."""
+        pool = getattr(self, "_strips", None)
+        return 0 if pool is None else pool.high_water
+
+    def _strip_pool(self):
+        if getattr(self, "_strips", None) is None:
+            self._strips = _StripPool(self.dev)
+        return self._strips
+
+    def _inter_geometry(self, ca, cb):
+        s1, e1 = int(self.offsets[ca]), int(self.offsets[ca + 1])
+        s2, e2 = int(self.offsets[cb]), int(self.offsets[cb + 1])
+        return s1, e1, s2, e2
+
+    def inter_median(self, ca, cb, stream=None):
+        """The median _stage_inter scales the trans block (ca, cb) by (cs_csr_median on the view of the whole block)."""
+        self._need_weights()
+        with self.dev.lock:
+            dev, lib = self.dev, self.dev.lib
+            s1, e1, s2, e2 = self._inter_geometry(ca, cb)
+            n_r, n_c = e1 - s1, e2 - s2
+            ext = self._ext.get(16 * n_r + 512)
+            d_begin, d_end = ext, ext + 8 * n_r
+            raw = self._view(s1, e1, s2, e2)
+            dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
+            view = self._view(s1, e1, s2, e2, d_begin, d_end)
+            med = C.c_double(0.0)
+            dev._check(lib.cs_csr_median(dev.ctx, stream, C.byref(view), C.byref(med)))
+            return med.value
+
+    def _stage_inter_rows(self, ca, cb, rows, largest_kernel=None, median=None, name=None, stream=None, dtype=np.float64):
+        dev, lib = self.dev, self.dev.lib
+        s1, e1, s2, e2 = self._inter_geometry(ca, cb)
+        n_r, n_c = e1 - s1, e2 - s2
+        a, b = int(rows[0]), int(rows[1])
+        if not (0 <= a < b <= n_r):
+            raise ValueError("row window outside the block")
+        if largest_kernel is None:
+            raise ValueError("a row strip needs largest_kernel (its halo)")
+        halo = (int(largest_kernel) - 1) // 2
+        ra, rb = _strip_rows(n_r, (a, b), halo)
+        m = rb - ra
+        ld = _inter_ld(n_c)
+        if m * ld > _MAX_STRIP_ELEMENTS:
+            raise ValueError(f"a strip of {m} rows x {ld} is above 2^31 elements: cut the block into more strips")
+        if median is None:
+            median = self.inter_median(ca, cb, stream=stream)
+        n_law = max(n_r, n_c)
+        ext = self._ext.get(16 * m + 8 * n_law + 512)
+        d_begin, d_end, d_law = ext, ext + 8 * m, ext + 16 * m
+        # a view of the rows ra .. rb - 1 (row r of the view = row ra + r of the block), the columns of chromosome cb
+        raw = self._view(s1 + ra, s1 + rb, s2, e2)
+        dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
+        view = self._view(s1 + ra, s1 + rb, s2, e2, d_begin, d_end)
+        scale = np.full(n_law, float(median))
+        dev._check(lib.cs_memcpy_h2d(dev.ctx, d_law, scale.ctypes.data, scale.nbytes, stream))
+        esz = np.dtype(dtype).itemsize
+        buf = self._strip_pool().take(m * ld * esz)
+        # (the scatter addresses the view's own rows; the block's matrix carries row0 = ra.  value / median, NaN -> 0, as _stage_inter)
+        dev._check(lib.cs_csr_to_band(dev.ctx, stream, C.byref(view), d_law, n_law, 0.0,
+                                      C.byref(CsMatrix(buf.ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0, 0))))
+        sig = CsMatrix(buf.ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0, ra)
+        block = StagedBlock(name or f"{self.names[ca]}-{self.names[cb]}", sig, (n_r, n_c), _Ptr(self.miss.ptr + s1),
+                            _Ptr(self.miss.ptr + s2), None, True, None)
+        block.row_window = (a, b)
+        block.view, block.view_row0 = view, ra
+        block.strip_pool = self._strips                  # (the pool owns the buffer; the strip is valid until the next staging)
+        return block
 
     def _stage_intra(self, ci, max_dist, largest_kernel, smooth=False, band_dtype=np.float64, name=None, stream=None,
                      resident=False, rows=None, reduce=None, dev=None, ext=None):
@@ -947,6 +1082,164 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
     return done(cid.accept_many(blocks, rec, windows, counts, engine.KernelSpec(kernel, tsvd), kernel_config, pvals=True))
 
 
+def _strip_reach(kernels):
+    """The template side whose halo a row strip of a trans block needs for these templates: (reach - 1) // 2 rows cover the
+    windows of the rows it owns, plus |kh - kw| for a non-square template (in full mode its score is read kh - kw rows away:
+    detection._offset_scores)."""
+    reach = 1
+    for k in kernels:
+        km, kn = np.shape(k)
+        kh, kw = (km - 1) // 2, (kn - 1) // 2
+        reach = max(reach, 2 * (kh + abs(kh - kw)) + 1)
+    return reach
+
+
+def _check_budget(inter_budget):
+    if inter_budget is None:
+        return INTER_BUDGET_DEFAULT
+    if not inter_budget > 0:
+        raise ValueError("inter_budget must be a positive number of bytes")
+    return inter_budget
+
+
+def _strip_common(block, kernel_config):
+    return dict(inter=True, full=True, sym_upper=False, max_dist=None, missing_tol=kernel_config["max_perc_undetected"] / 100,
+                mask_mode=MASK_BINS, miss_row=block.miss_row, miss_col=block.miss_col)
+
+
+def detect_inter_block(dcool, ca, cb, kernel_config, kernel, tsvd=None, want_windows=True, inter_budget=None, reach=None, median=None,
+                       stats=None):
+    """detect_block(raw=True) of the trans block (ca, cb) without staging it whole: row strips of at most inter_budget bytes
+    (plan_inter_strips), staged one at a time in the strip pool, each scanned only on the output tiles a stored pixel reaches
+    (cs_csr_tile_occupancy -> cs_candidates_tiles); the strips' candidates are concatenated and labelled once (cs_label_foci),
+    and each strip scores the foci whose row it owns (cs_quantify_pixels) -- the cut-merging of detection.detect_split_on_device
+    with a local concatenation for its all-gather, so foci across a cut come out as from one piece.  Returns (table (k, 4),
+    windows) or (None, None).  reach: template side of the halo (_strip_reach); median: the block's (inter_median).  stats: a
+    dict that receives strips / tiles / tiles_listed."""
+    kernel = np.asarray(kernel, dtype=np.float64)
+    budget = _check_budget(inter_budget)
+    s1, e1, s2, e2 = dcool._inter_geometry(ca, cb)
+    n_r, n_c = e1 - s1, e2 - s2
+    if min(n_r, n_c) <= max(kernel.shape):
+        return None, None
+    _check_template(kernel)
+    kspec = engine.KernelSpec(kernel, tsvd)
+    km, kn = kspec.km, kspec.kn
+    reach = max(reach or 1, _strip_reach([kernel]))
+    strips = plan_inter_strips(n_r, n_c, budget, (reach - 1) // 2)
+    if median is None:
+        median = dcool.inter_median(ca, cb)
+    dev = dcool.dev
+    tiles_x = -(-n_c // 64)
+    n_tiles = n_listed = 0
+    rows_l, cols_l, vals_l = [], [], []
+    held = None
+    for rows in strips:
+        held = None                                      # (the pool's buffer is restaged below)
+        blk = dcool.stage_inter(ca, cb, rows=rows, largest_kernel=reach, median=median)
+        tiles, nt = engine.run_tile_occupancy(dev, blk.view, blk.view_row0, km, kn, rows, n_c)
+        n_tiles += tiles_x * -(-(rows[1] - rows[0]) // 64)
+        n_listed += nt
+        r, c, v = engine.run_candidates_tiles(dev, blk.sig, (n_r, n_c), kspec, rows, tiles, nt, pearson=kernel_config["pearson"],
+                                              lo_diag=-(n_r - 1), hi_diag=n_c - 1, **_strip_common(blk, kernel_config))
+        rows_l.append(r)
+        cols_l.append(c)
+        vals_l.append(v)
+        held = blk
+    if stats is not None:
+        stats.update(strips=len(strips), tiles=n_tiles, tiles_listed=n_listed)
+    cand_r, cand_c, cand_v = np.concatenate(rows_l), np.concatenate(cols_l), np.concatenate(vals_l)
+    if cand_r.size == 0:
+        return None, None
+    f_rows, f_cols, f_size = engine.run_label_foci(dev, (n_r, n_c), cand_r, cand_c, cand_v, min_size=2, diag_only=0)
+    if f_rows.size == 0:
+        return None, None
+    rec = np.zeros(f_rows.size, dtype=FOCUS_DTYPE)
+    windows = np.zeros((f_rows.size, km, kn)) if want_windows else None
+    conv = [np.zeros(f_rows.size, dtype=np.int64), np.zeros(f_rows.size, dtype=np.int64), np.zeros(f_rows.size)] if km != kn else None
+    for rows in strips:
+        mine = (f_rows >= rows[0]) & (f_rows < rows[1])
+        if not mine.any():
+            continue
+        blk = held if held is not None and held.row_window == tuple(rows) else \
+            dcool.stage_inter(ca, cb, rows=rows, largest_kernel=reach, median=median)
+        common = _strip_common(blk, kernel_config)
+        r, w = engine.run_quantify_pixels(dev, blk.sig, (n_r, n_c), kspec, f_rows[mine], f_cols[mine], want_windows=want_windows,
+                                          **common)
+        r["focus_size"] = f_size[mine]
+        rec[mine] = r
+        if want_windows:
+            windows[mine] = w
+        if conv is not None:
+            rr_m, cc_m = r["bin1"].astype(np.int64), r["bin2"].astype(np.int64)
+            for k, part in enumerate(cid._offset_scores(dev, blk.sig, (n_r, n_c), kspec, rr_m, cc_m, dict(common, stream=None))):
+                conv[k][mine] = part
+        held = blk
+    rr, cc = rec["bin1"].astype(np.int64), rec["bin2"].astype(np.int64)
+    return cid._accept_records(rec, windows, rr, cc, "detect", (n_r, n_c), kspec, kernel_config, inter=True, max_dist=None, full=True,
+                               raw=True, conv=None if conv is None else tuple(conv))
+
+
+def _row_groups(rows, n_r, n_c, budget, halo):
+    """Groups of the (sorted, unique) rows that hold quantify positions: each (a, b) is staged as one strip (rows a - halo ..
+    b + halo - 1) within `budget` bytes and below 2^31 elements."""
+    ld = _inter_ld(n_c)
+    max_rows = min(int(budget) // (ld * 8), _MAX_STRIP_ELEMENTS // ld)
+    if max_rows < 1 + 2 * halo and max_rows < n_r:
+        raise ValueError(f"inter_budget of {int(budget)} bytes cannot hold one row and its halo of {halo} rows of a block of {n_c} columns")
+    groups, a = [], None
+    for r in rows.tolist():
+        if a is not None:
+            lo, hi = _strip_rows(n_r, (a, r + 1), halo)
+            if hi - lo <= max_rows:
+                b = r + 1
+                continue
+            groups.append((a, b))
+        a, b = r, r + 1
+    if a is not None:
+        groups.append((a, b))
+    return groups
+
+
+def quantify_inter_block(dcool, ca, cb, coords, kernels, kernel_config, tsvd=None, inter_budget=None, median=None):
+    """The positions `coords` ((n, 2) block-local rows and columns) of the trans block (ca, cb) scored with every template, as
+    quantify scores them on the whole block, staging only the rows that hold a position (plus the halo), grouped into strips
+    within inter_budget bytes.  Returns, per template, (table (n, 4): bin1, bin2, score, pvalue; windows (n, km, kn))."""
+    budget = _check_budget(inter_budget)
+    kernels = [np.asarray(k, dtype=np.float64) for k in kernels]
+    km, kn = kernels[0].shape
+    s1, e1, s2, e2 = dcool._inter_geometry(ca, cb)
+    n_r, n_c = e1 - s1, e2 - s2
+    coords = np.asarray(coords, dtype=np.int64).reshape(-1, 2)
+    n = coords.shape[0]
+    out = [(np.full((n, 4), np.nan), np.full((n, km, kn), np.nan)) for _ in kernels]
+    if n == 0 or min(n_r, n_c) <= max(km, kn):
+        return out
+    reach = _strip_reach(kernels)
+    halo = (reach - 1) // 2
+    if median is None:
+        median = dcool.inter_median(ca, cb)
+    row_of = np.clip(coords[:, 0], 0, n_r - 1)
+    batch = tsvd is None and not os.environ.get("CHROMOSIGHT_HIP_NO_QUANTIFY_BATCH")
+    if batch:
+        for k in kernels:
+            _check_template(k)
+    specs = [engine.KernelSpec(k, tsvd) for k in kernels]
+    for a, b in _row_groups(np.unique(row_of), n_r, n_c, budget, halo):
+        sel = np.flatnonzero((row_of >= a) & (row_of < b))
+        blk = dcool.stage_inter(ca, cb, rows=(a, b), largest_kernel=reach, median=median)
+        res = cid.quantify_many_on_device(dcool.dev, [blk], specs, kernel_config, [coords[sel]]) if batch else None
+        for t, kspec in enumerate(specs):
+            if res is not None:
+                table, wins = res[t]
+            else:
+                table, wins = cid.detect_on_device(dcool.dev, blk.sig, blk.shape, kspec, kernel_config, blk.miss_row, blk.miss_col,
+                                                   inter=True, max_dist=None, full=True, coords=coords[sel].copy(), raw=True)
+            out[t][0][sel] = table
+            out[t][1][sel] = wins
+    return out
+
+
 def detect_blocks_templates(dcool, blocks, kernel_config, kernels, want_windows=False, dev=None, stream=None, begin_only=False):
     """A 1-D pattern's templates (one size: the three borders templates, the one hairpins template) on banded intra blocks with ONE native call
     (cs_detect_foci_batch_templates) instead of one launch chain per template.  Returns a callable that yields, per template,
@@ -1016,13 +1309,16 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
 
 def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, inter=False, subsample=None, seed=0,
-           return_windows=False, win_size=None):
+           return_windows=False, win_size=None, inter_budget=None):
     """`chromosight detect` (balanced matrix) on a decoded cool (dict) or a DeviceCool; options
     --inter, --smooth-trend, --tsvd, --subsample (seeded), --iterations through the config.  Every
     block is staged once in HBM (distance law, detrend, band / median scaling) and stays resident
     across templates and iterations; each (block, template) is one native call.
     Returns the output table (same columns and row order as the reference's <prefix>.tsv); with
-    return_windows also the windows of its rows (what the reference saves as <prefix>.json / .npy)."""
+    return_windows also the windows of its rows (what the reference saves as <prefix>.json / .npy).
+    With inter, the trans blocks are not resident: each is scanned in row strips of at most inter_budget bytes
+    (default INTER_BUDGET_DEFAULT) by detect_inter_block, one block at a time."""
+    budget = _check_budget(inter_budget)
     kernel_config = with_win_size(kernel_config, win_size)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
     if subsample is not None:
@@ -1051,14 +1347,22 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
     pairs = sub_matrices(dcool, inter)
     intra = dict(zip([a for a, b in pairs if a == b],
                      dcool.stage_blocks([a for a, b in pairs if a == b], max_dist, largest, smooth=smooth, band_dtype=band_dtype)))
-    blocks = [intra[a] if a == b else dcool.stage_inter(a, b, resident=True) for a, b in pairs]
+    # trans blocks: staged strip by strip for every template and iteration (detect_inter_block), scaled by their median
+    trans = [(a, b) for a, b in pairs if a != b]
+    medians = {pair: dcool.inter_median(*pair) for pair in trans}
+    reach = _strip_reach(kernel_config["kernels"])
+    blocks = [intra[a] for a, b in pairs if a == b]
     all_coords, all_windows = [], []
     for kernel_id, kernel in enumerate(kernel_config["kernels"]):
         for it in range(kernel_config["max_iterations"]):
             tables, windows = [], []
             # windows feed the next iteration's template and the optional output; otherwise they stay on the device
             need_windows = return_windows or it + 1 < kernel_config["max_iterations"]
-            results = detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=tsvd, raw=True, want_windows=need_windows)
+            cis = iter(detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=tsvd, raw=True, want_windows=need_windows) if blocks else [])
+            results = [next(cis) if a == b else
+                       detect_inter_block(dcool, a, b, kernel_config, kernel, tsvd=tsvd, want_windows=need_windows, inter_budget=budget,
+                                          reach=reach, median=medians[(a, b)])
+                       for a, b in pairs]
             for (ca, cb), (tab, win) in zip(pairs, results):
                 if tab is None or len(tab) == 0:
                     continue
@@ -1076,6 +1380,8 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
                 kernel_windows = np.concatenate(windows, axis=0)
                 all_windows.append(kernel_windows)
                 kernel = cid.pileup_patterns(kernel_windows)
+    if trans:
+        dcool._strip_pool().release()
     if not all_coords:
         empty = pd.DataFrame(columns=OUTPUT_COLUMNS)
         return (empty, np.zeros((0,) + np.shape(kernel_config["kernels"][0]))) if return_windows else empty
@@ -1130,12 +1436,15 @@ def postprocess(coords, kernel_config, binsize, off, names, bin_start, bin_end, 
 
 
 def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=None, seed=0, smooth=False,
-             max_dist_bp=None, win_size=None, shard=None):
+             max_dist_bp=None, win_size=None, shard=None, inter_budget=None):
     """`chromosight quantify` (cli/chromosight.py:264-470): score the given 2-D positions with every
     template of the config and keep, per position, the row the reference keeps (sorted by score,
     last of each (chrom1, start1, chrom2, start2) group).  `positions`: DataFrame with chrom1, start1,
     end1, chrom2, start2, end2.  Returns (table in the reference's output order and columns, windows).
-    shard: parallel.QuantifyShard -- the sub-matrices are dealt to the ranks (parallel.quantify_genome)."""
+    shard: parallel.QuantifyShard -- the sub-matrices are dealt to the ranks (parallel.quantify_genome).
+    With inter (and no shard), a trans block is never staged whole: only the rows that hold a position, plus the halo, in
+    strips of at most inter_budget bytes (quantify_inter_block)."""
+    budget = _check_budget(inter_budget)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
     if subsample is not None:
         dcool = dcool.subsampled(subsample, seed=seed, inter=inter)
@@ -1196,6 +1505,9 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
     # Sharded run (parallel.quantify_genome): this rank scores the positions of its own sub-matrices, the scores of all ranks
     # are exchanged once below -- the reference's pool over sub-matrices (cli/chromosight.py:396-410)
     mine = todo if shard is None else shard.select(todo, dcool, max_dist)
+    strips = [] if shard is not None else [t for t in mine if t[0] != t[1]]
+    if strips:
+        mine = [t for t in mine if t[0] == t[1]]
     # every sub-matrix that holds a position is staged once: the intra blocks with ONE native call (cs_stage_blocks)
     staged = {}
     intra = sorted({ca for ca, cb, _, _ in mine if ca == cb})
@@ -1237,6 +1549,19 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
             score_out[kernel_id][sel] = rec[:, 2]
             pval_out[kernel_id][sel] = rec[:, 3]
             win_array(kernel_id)[sel] = wins
+    if strips:
+        for k in range(len(kernels)):
+            if win_src[k] is not None:                  # (the batched windows in position order beside the trans blocks' below)
+                wins, where = win_src[k]
+                win_array(k)[where] = wins
+                win_src[k] = None
+        for ca, cb, sel, coords in strips:
+            res = quantify_inter_block(dcool, ca, cb, coords, kernels, cfg, tsvd=tsvd, inter_budget=budget)
+            for kernel_id, (table, wins) in enumerate(res):
+                score_out[kernel_id][sel] = table[:, 2]
+                pval_out[kernel_id][sel] = table[:, 3]
+                win_array(kernel_id)[sel] = wins
+        dcool._strip_pool().release()
     if shard is not None:
         win_out = [win_array(k) for k in range(len(kernels))]
         score_out, pval_out, win_out = shard.merge(score_out, pval_out, win_out, [sel for _, _, sel, _ in mine])

@@ -92,7 +92,7 @@ const char* cs_version(void);
  * cs_detect_foci / cs_candidates) on this context: diagnostics, and what the tests use to make sure
  * the intended native path ran */
 enum { CS_KERNEL_NONE = 0, CS_KERNEL_GENERIC = 1, CS_KERNEL_STREAM = 2, CS_KERNEL_MFMA = 3, CS_KERNEL_MFMA_DENSE = 4,
-       CS_KERNEL_MFMA_REG = 5, CS_KERNEL_SEPARABLE = 6, CS_KERNEL_MFMA_WIDE = 7 };
+       CS_KERNEL_MFMA_REG = 5, CS_KERNEL_SEPARABLE = 6, CS_KERNEL_MFMA_WIDE = 7, CS_KERNEL_MFMA_LIST = 8 };
 int cs_last_kernel(const cs_ctx* ctx);
 /* Range guard of the device entries (off by default).  The reference sums every window on its own
  * (detection.py:1002-1018) and zeroes exactly the windows that hold a non-finite pixel (:1088-1101); the device kernels
@@ -507,6 +507,24 @@ int cs_candidates(cs_ctx* ctx, void* stream, const cs_matrix* signal, const cs_k
 int cs_label_foci(cs_ctx* ctx, void* stream, int32_t ms, int32_t ns, const int32_t* h_rows,
                   const int32_t* h_cols, const double* h_vals, int64_t n, int32_t min_size, int32_t diag_only,
                   int32_t* h_foci_rows, int32_t* h_foci_cols, int32_t* h_foci_size, int64_t cap, int64_t* n_foci);
+
+/* ---- Trans blocks in row strips: only the tiles a stored pixel reaches.
+ *
+ * cs_csr_tile_occupancy: the 64 x 64 output tiles of a dense map of mat->n_cols columns -- tile (ty, tx) holds the output rows
+ * row_begin + 64 ty .. + 63 (below row_end) and columns 64 tx .. + 63 -- whose windows of a km x kn template (odd, <= 65) reach a
+ * pixel of the view `mat` with count > 0 and finite row and column weights (view row r is row row_off + r of the map): a window
+ * without one is 0 after staging, its coefficient is 0, never a candidate.  Integer bitmap, then an ordered compaction:
+ * d_tiles (device, cap entries) receives the tile indices ty * ceil(n_cols / 64) + tx in increasing order, *n_tiles their
+ * number (CS_ERR_OVERFLOW when above cap).  Synchronous.
+ *
+ * cs_candidates_tiles: cs_candidates (dense signal) restricted to the n_tiles tiles of the device list d_tiles (indices of the
+ * grid above for params->row_begin / row_end; any order, no repeats): the persistent workgroups of the masked tile kernel take
+ * their tiles from the list; the pixels of other tiles are not candidates.  n_tiles = 0: no candidate, nothing launched. */
+int cs_csr_tile_occupancy(cs_ctx* ctx, void* stream, const cs_csr* mat, int32_t row_off, int32_t km, int32_t kn, int32_t row_begin,
+                          int32_t row_end, int32_t* d_tiles, int64_t cap, int64_t* n_tiles);
+int cs_candidates_tiles(cs_ctx* ctx, void* stream, const cs_matrix* signal, const cs_kernel* kernel,
+                        const cs_normxcorr2_params* params, const cs_foci_params* foci, const int32_t* d_tiles, int32_t n_tiles,
+                        int32_t* h_rows, int32_t* h_cols, double* h_vals, int64_t cap, int64_t* n);
 
 /* ---- a genome step as ONE native call -------------------------------------------------------------------------------
  * The entries above are what a detect step is made of -- cs_stage_blocks, an event, cs_detect_foci_blocks for the 2-D
