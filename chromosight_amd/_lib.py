@@ -150,6 +150,24 @@ class CsIceSpanStats(C.Structure):
     ]
 
 
+class CsSubsampleParams(C.Structure):
+    _fields_ = [
+        ("sample", C.c_double),
+        ("seed", C.c_uint64),
+        ("inter", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class CsSubsampleBlock(C.Structure):
+    _fields_ = [
+        ("chrom1", C.c_int32),
+        ("chrom2", C.c_int32),
+        ("total", C.c_int64),
+        ("keep", C.c_int64),
+    ]
+
+
 class CsCall(C.Structure):
     """One entry of a cs_run_calls list (include/chromosight_hip.h)."""
     _fields_ = [
@@ -238,6 +256,9 @@ _PROTOTYPES = {
     "cs_csr_median_many": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.c_int32, C.POINTER(C.c_double)]),
     "cs_ice_balance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32,
                                  C.POINTER(CsIceParams), C.c_void_p, C.POINTER(CsIceSpanStats)]),
+    "cs_subsample": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32,
+                               C.POINTER(CsSubsampleParams), C.POINTER(CsCsr), C.POINTER(C.c_int64), C.POINTER(CsSubsampleBlock),
+                               C.c_void_p]),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

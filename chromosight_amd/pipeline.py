@@ -395,18 +395,45 @@ class DeviceCool:
         self.indptr = dev.to_device(indptr, np.int64)
         self.indices = dev.to_device(b2, np.int32)
         self.data = dev.to_device(cnt, self.val_dtype)
-        self.host = {"binsize": self.binsize, "chrom_offset": off, "chrom_names": np.asarray(self.names), "bin1_id": b1,
-                     "bin2_id": b2, "count": cnt, "weight": None, "bin_start": self.bin_start, "bin_end": self.bin_end}
+        self._host = {"binsize": self.binsize, "chrom_offset": off, "chrom_names": np.asarray(self.names), "bin1_id": b1,
+                      "bin2_id": b2, "count": cnt, "weight": None, "bin_start": self.bin_start, "bin_end": self.bin_end}
+        # what cs_stage_blocks needs: every stored pixel on or above the diagonal (a .cool's symmetric-upper storage)
+        self.upper = bool(b1.size == 0 or np.all(b2 >= b1))
+        self._init_resident(weight)
+
+    @classmethod
+    def from_device_csr(cls, parent, indptr, indices, data, nnz, val_dtype):
+        """A DeviceCool over a pixel table already in HBM (device buffers of the CSR: n_bins + 1 row pointers, column bins and
+        counts, the first `nnz` entries used -- the result of subsample.subsample_csr), with `parent`'s bins, names and weights.
+        The counts are non-negative integers: val_dtype is float32 when they are all below 2^24, as the constructor would
+        choose for an upload of the same table.  `.host` is downloaded once, when first read."""
+        self = cls.__new__(cls)
+        self.dev = parent.dev
+        self.offsets = parent.offsets
+        self.n_bins = parent.n_bins
+        self.names = list(parent.names)
+        self.binsize = parent.binsize
+        self.bin_start, self.bin_end = parent.bin_start, parent.bin_end
+        self.val_dtype = np.dtype(val_dtype).type
+        self._counts_exact = self.val_dtype is np.float32
+        self.nnz = int(nnz)
+        self.indptr, self.indices, self.data = indptr, indices, data
+        self._host, self._host_weight = None, parent.host_weight
+        # a subset of an upper-triangle table is one; anything else is checked on the pixels
+        self.upper = True if parent.upper else bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]))
+        self._init_resident(parent.host_weight)
+        return self
+
+    def _init_resident(self, weight):
+        self._host_weight = None
         self._retired = []
         self.weight = self.miss = self.det = self.miss_host = None
         self.counts_ok = False
         self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes
         if weight is not None:
             self.set_weights(weight)
-        # what cs_stage_blocks needs: every stored pixel on or above the diagonal (a .cool's symmetric-upper storage)
-        self.upper = bool(b1.size == 0 or np.all(b2 >= b1))
-        self._band = _Scratch(dev)
-        self._ext = _Scratch(dev)
+        self._band = _Scratch(self.dev)
+        self._ext = _Scratch(self.dev)
         self._stage_lock = threading.RLock()
         self._free = _FreeList()        # HBM of released resident blocks, reused by the next staging
         self._workers = None
@@ -427,8 +454,30 @@ class DeviceCool:
         self.miss_host = miss
         self.miss = dev.to_device(miss.astype(np.uint8))
         self.det = dev.to_device((~miss).astype(np.uint8))
-        self.host["weight"] = weight
+        self._host_weight = weight
+        if self._host is not None:
+            self._host["weight"] = weight
         self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes + self.weight.nbytes
+
+    @property
+    def host(self):
+        """The pixel table as a decoded-cool dictionary (bin1_id, bin2_id, count, weight, ...).  A table built on the device
+        (from_device_csr) downloads it here, once."""
+        if self._host is None:
+            n = int(self.nnz)
+            indptr = self.indptr.download()
+            b1 = np.repeat(np.arange(self.n_bins, dtype=np.int64), np.diff(indptr))
+            b2 = self.indices.download()[:n].astype(np.int64)
+            cnt = self.data.download().view(self.val_dtype)[:n].astype(np.int64)
+            self._host = {"binsize": self.binsize, "chrom_offset": self.offsets, "chrom_names": np.asarray(self.names), "bin1_id": b1,
+                          "bin2_id": b2, "count": cnt, "weight": self._host_weight, "bin_start": self.bin_start,
+                          "bin_end": self.bin_end}
+        return self._host
+
+    @property
+    def host_weight(self):
+        """The balancing weights on the host (None before set_weights)."""
+        return self._host_weight
 
     @property
     def has_weights(self):
@@ -905,13 +954,20 @@ class DeviceCool:
                 out.append(block)
             return out
 
-    def subsampled(self, sample, seed=0, inter=False):
+    def subsampled(self, sample, seed=0, inter=False, sampler="numpy"):
         """A DeviceCool whose counts are a random subsample of this one's, drawn per sub-matrix without
         replacement like the reference's --subsample (contacts_map.py:552-596, preprocessing.py:359-401):
         `sample` in (0, 1] is the proportion of the contacts of every sub-matrix to keep.  Intra blocks
         are sampled as the reference sees them (symmetric matrix, both triangles drawn independently;
         the path then only reads the upper one).  Unlike the reference's unseeded np.random.choice the
-        draw is reproducible: numpy Generator(seed), multivariate hypergeometric."""
+        draw is reproducible: numpy Generator(seed), multivariate hypergeometric.
+        sampler="device" draws the same pools on the device (chromosight_amd/subsample.py: exact hypergeometric split trees,
+        counter-based uniforms): another table for a given seed than "numpy", the same on every device; the result stays in HBM."""
+        if sampler not in ("numpy", "device"):
+            raise ValueError(f"sampler must be 'numpy' or 'device', got {sampler!r}")
+        if sampler == "device":
+            from .subsample import subsample_device
+            return subsample_device(self, sample, seed=seed, inter=inter)
         sample = float(sample)
         if sample < 0:
             raise ValueError("Subsample must be strictly positive.")
@@ -1309,7 +1365,7 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
 
 def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, inter=False, subsample=None, seed=0,
-           return_windows=False, win_size=None, inter_budget=None):
+           return_windows=False, win_size=None, inter_budget=None, sampler="numpy"):
     """`chromosight detect` (balanced matrix) on a decoded cool (dict) or a DeviceCool; options
     --inter, --smooth-trend, --tsvd, --subsample (seeded), --iterations through the config.  Every
     block is staged once in HBM (distance law, detrend, band / median scaling) and stays resident
@@ -1317,12 +1373,13 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
     Returns the output table (same columns and row order as the reference's <prefix>.tsv); with
     return_windows also the windows of its rows (what the reference saves as <prefix>.json / .npy).
     With inter, the trans blocks are not resident: each is scanned in row strips of at most inter_budget bytes
-    (default INTER_BUDGET_DEFAULT) by detect_inter_block, one block at a time."""
+    (default INTER_BUDGET_DEFAULT) by detect_inter_block, one block at a time.
+    sampler: how --subsample draws, "numpy" (the host path) or "device" (DeviceCool.subsampled)."""
     budget = _check_budget(inter_budget)
     kernel_config = with_win_size(kernel_config, win_size)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
     if subsample is not None:
-        dcool = dcool.subsampled(subsample, seed=seed, inter=inter)
+        dcool = dcool.subsampled(subsample, seed=seed, inter=inter, sampler=sampler)
     binsize = dcool.binsize
     off = dcool.offsets
     names = dcool.names
@@ -1436,18 +1493,19 @@ def postprocess(coords, kernel_config, binsize, off, names, bin_start, bin_end, 
 
 
 def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=None, seed=0, smooth=False,
-             max_dist_bp=None, win_size=None, shard=None, inter_budget=None):
+             max_dist_bp=None, win_size=None, shard=None, inter_budget=None, sampler="numpy"):
     """`chromosight quantify` (cli/chromosight.py:264-470): score the given 2-D positions with every
     template of the config and keep, per position, the row the reference keeps (sorted by score,
     last of each (chrom1, start1, chrom2, start2) group).  `positions`: DataFrame with chrom1, start1,
     end1, chrom2, start2, end2.  Returns (table in the reference's output order and columns, windows).
     shard: parallel.QuantifyShard -- the sub-matrices are dealt to the ranks (parallel.quantify_genome).
     With inter (and no shard), a trans block is never staged whole: only the rows that hold a position, plus the halo, in
-    strips of at most inter_budget bytes (quantify_inter_block)."""
+    strips of at most inter_budget bytes (quantify_inter_block).  sampler: how --subsample draws, "numpy" or "device"
+    (DeviceCool.subsampled)."""
     budget = _check_budget(inter_budget)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
     if subsample is not None:
-        dcool = dcool.subsampled(subsample, seed=seed, inter=inter)
+        dcool = dcool.subsampled(subsample, seed=seed, inter=inter, sampler=sampler)
     cfg = dict(with_win_size(kernel_config, win_size))
     bed2d = positions.loc[:, ["chrom1", "start1", "end1", "chrom2", "start2", "end2"]].reset_index(drop=True).copy()
     furthest = np.max(bed2d.start2 - bed2d.start1)

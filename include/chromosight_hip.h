@@ -371,6 +371,36 @@ typedef struct {
 int cs_ice_balance(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t* chrom_offsets, int32_t n_chrom,
                    const cs_ice_params* params, double* d_bias, cs_ice_span_stats* h_stats);
 
+/* ---- `--subsample` on the device: every sub-matrix of the resident pixel table keeps an exact multivariate hypergeometric sample
+ * of int(sample * total) of its contacts (the reference's preprocessing.py:359-401 subsample_contacts on every block,
+ * contacts_map.py:555-596) ---- */
+typedef struct {
+    double sample;             /* proportion kept, 0 <= sample <= 1 */
+    uint64_t seed;             /* the draw is a pure function of (seed, table): any launch shape, context or device gives the same */
+    int32_t inter;             /* 1: trans blocks (a < b) are sampled too; 0: their pixels are dropped from the result */
+    int32_t reserved;          /* 0 */
+} cs_subsample_params;
+typedef struct {
+    int32_t chrom1, chrom2;    /* the sub-matrix */
+    int64_t total;             /* contacts of its pool: trans block = its counts; intra block = upper triangle + mirror copies */
+    int64_t keep;              /* int(sample * total): the contacts drawn from the pool */
+} cs_subsample_block;
+/* genome: the resident upper-triangle pixel table (square, plain row pointers, no weights, nnz < 2^31 - 1); counts are truncated to
+ * integers (NaN, inf, negative or >= 2^62: CS_ERR_INVALID).  chrom_offsets: n_chrom + 1 host values from 0 to n_rows.  Pools: an
+ * intra block is its upper-triangle pixels plus a mirror copy of every off-diagonal one (the symmetric matrix), of which only the
+ * upper copy's draw is stored; a trans block (inter = 1) is its pixels.  The draw of a pool is a binary split tree over its pixels
+ * in table order (Hypergeometric(N_left, N_right, k) at every node, Hypergeometric(c, c, t) between a pixel and its mirror) with
+ * Philox4x32-10 uniforms keyed by the seed and counting over (block, node, draw): exact inversion / HRUA draws, int64 throughout.
+ * out: caller-allocated d_indptr (n_rows + 1), d_indices and d_data with room for genome->nnz entries (8 bytes each in d_data);
+ * the call sets n_rows, n_cols, nnz (= *h_out_nnz) and dtype (CS_F32 when every kept count is below 2^24, else CS_F64) and
+ * writes the pixels with a count > 0 in table order (an ordered scan, no atomics).  h_blocks: the sampled blocks in (chrom1,
+ * chrom2) row-major order -- n_chrom entries, or n_chrom (n_chrom + 1) / 2 with inter -- empty ones included.  d_drawn: NULL or
+ * genome->nnz int64 receiving each pixel's share of its pool draw before the upper / mirror split (0 outside the sampled blocks).
+ * Synchronous; the table is never written. */
+int cs_subsample(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t* chrom_offsets, int32_t n_chrom,
+                 const cs_subsample_params* params, cs_csr* out, int64_t* h_out_nnz, cs_subsample_block* h_blocks,
+                 int64_t* d_drawn);
+
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
     double pearson;         /* candidate threshold: coefficient >= pearson and != 0 (detection.py:417-421) */
