@@ -362,6 +362,70 @@ int ensure_wfrag_wide(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaW
     return CS_OK;
 }
 
+// The image of the kernel of the templates of 34 .. 81 (cs_corr_large.hip; layout in cs_launch.h MfmaLargeWeights): three sets
+// x km rows x NP passes x {head, tail} x 1 KiB (1.5 MB at 81 x 81: L2-resident).
+int ensure_wfrag_large(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaLargeWeights* E)
+{
+    const std::vector<unsigned char>& key = ctx->w_cached[0];
+    const int kk = km * kn;
+    const size_t n_floats = key.size() / 4;
+    if (kk <= 0 || n_floats < (size_t)kk) return fail(ctx, CS_ERR_INVALID, "weights missing for the matrix-core kernel");
+    if (!cs::corr_mfma_large_fits(km, kn)) return fail(ctx, CS_ERR_INVALID, "the large-template matrix-core kernel holds templates of 34 .. 81");
+    const int np = cs::corr_mfma_large_passes(kn);
+    const int nsets = (int)std::min<size_t>(3, n_floats / kk);
+    const size_t bytes = (size_t)3 * km * np * 2 * 512 * 2;
+    if (bytes > ctx->d_wfrag_large_bytes) {
+        if (ctx->d_wfrag_large) {
+            CS_HIP(ctx, hipDeviceSynchronize());   // a queued kernel may still read the old image
+            CS_HIP(ctx, hipFree(ctx->d_wfrag_large));
+        }
+        ctx->d_wfrag_large = nullptr;
+        ctx->d_wfrag_large_bytes = 0;
+        ctx->wfrag_large_key.clear();
+        CS_HIP(ctx, hipMalloc(&ctx->d_wfrag_large, bytes));
+        ctx->d_wfrag_large_bytes = bytes;
+    }
+    if (!(ctx->wfrag_large_km == km && ctx->wfrag_large_kn == kn && ctx->wfrag_large_key == key)) {
+        const float* w = reinterpret_cast<const float*>(key.data());
+        std::vector<unsigned char> img(bytes, 0);
+        uint16_t* halfs = reinterpret_cast<uint16_t*>(img.data());
+        for (int set = 0; set < nsets; ++set) {
+            float amax = 0.0f;
+            for (int t = 0; t < kk; ++t) amax = std::max(amax, std::fabs(w[set * kk + t]));
+            int ew = 0;
+            if (amax > 0.0f && std::isfinite(amax)) {
+                int e2;
+                (void)std::frexp(amax, &e2);          // amax = f * 2^e2, f in [0.5, 1)
+                ew = 7 - e2;                           // amax * 2^ew in [64, 128)
+            }
+            ew = std::max(-100, std::min(100, ew));
+            ctx->wfrag_large_unscale[set] = std::ldexp(1.0f, -ew);
+            for (int s = 0; s < km; ++s)
+                for (int pass = 0; pass < np; ++pass)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int e = 0; e < 8; ++e) {
+                            const int t = 32 * pass + 8 * (lane >> 4) + e - (lane & 15);
+                            if (t < 0 || t >= kn) continue;
+                            const size_t base = ((((size_t)set * km + s) * np + pass) * 2) * 512;
+                            const float v = std::ldexp(w[set * kk + s * kn + t], ew);
+                            const uint16_t hb = f32_to_f16_bits(v);
+                            halfs[base + (size_t)lane * 8 + e] = hb;
+                            halfs[base + 512 + (size_t)lane * 8 + e] = f32_to_f16_bits(v - f16_bits_to_f32(hb));
+                        }
+        }
+        CS_HIP(ctx, hipMemcpyAsync(ctx->d_wfrag_large, img.data(), bytes, hipMemcpyHostToDevice, stream));
+        ++ctx->uploads;
+        CS_HIP(ctx, hipStreamSynchronize(stream));    // the pageable source dies here
+        ctx->wfrag_large_key = key;
+        ctx->wfrag_large_km = km;
+        ctx->wfrag_large_kn = kn;
+    }
+    E->frag = reinterpret_cast<const uint4*>(ctx->d_wfrag_large);
+    for (int set = 0; set < 3; ++set) E->unscale[set] = ctx->wfrag_large_unscale[set];
+    E->passes = np;
+    return CS_OK;
+}
+
 bool fast_available(int km, int kn, int* K);
 
 // Which float32 calls take the two-pass matrix-core kernel (cs_corr_wide.hip): templates with a side of 18 .. 33 -- what
@@ -376,6 +440,20 @@ bool mfma_wide_wanted(const cs::CorrArgs<float>& A)
     if (!A.out.ptr && !(A.cand_keys && A.cand_count && !A.defer_args && A.ks.cand_cmin > 0.0f)) return false;     // a map, or a candidate sink
     if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA") || std::getenv("CHROMOSIGHT_HIP_NO_WIDE")) return false;
     return true;
+}
+
+// Which float32 calls take the matrix-core kernel of the templates with a side of 34 .. 81 (cs_corr_large.hip): candidate
+// sinks without a map (cs_candidates, cs_candidates_tiles, the detect flow: the 81 x 81 `centromeres` template) in every
+// container the runtime-size kernel served.  Map calls stay on the runtime-size kernel unless CHROMOSIGHT_HIP_LARGE=1;
+// CHROMOSIGHT_HIP_NO_LARGE=1 / CHROMOSIGHT_HIP_NO_MFMA=1: never (the runtime-size kernel: the in-library cross-check).
+bool mfma_large_wanted(const cs::CorrArgs<float>& A)
+{
+    if (!cs::corr_mfma_large_fits(A.km, A.kn)) return false;
+    if (A.sig.counts || A.sig.layout == CS_LAYOUT_BAND_LAZY || A.defer_args) return false;
+    if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA") || std::getenv("CHROMOSIGHT_HIP_NO_LARGE")) return false;
+    if (!A.out.ptr) return A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f;          // a candidate sink
+    const char* e = std::getenv("CHROMOSIGHT_HIP_LARGE");
+    return e && e[0] == '1';
 }
 
 // Which float32 calls go to the matrix cores (cs_corr_mfma.hip).  Default: unmasked dense float32 maps
@@ -684,6 +762,20 @@ int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, 
         if (rc == -5) return CS_NEED_MAP;
         if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
         ctx->cand_fused = true;
+        return CS_OK;
+    }
+    if (allow_fast && mfma_large_wanted(A)) {
+        // template side 34 .. 81: candidate sinks (the kernel appends the candidates itself; a tile list is walked as listed)
+        // and, under CHROMOSIGHT_HIP_LARGE=1, maps
+        cs::MfmaLargeWeights E;
+        rc = ensure_wfrag_large(ctx, stream, A.km, A.kn, &E);
+        if (rc != CS_OK) return rc;
+        const bool sink = !A.out.ptr;
+        ctx->last_kernel = CS_KERNEL_MFMA_LARGE;
+        rc = cs::launch_corr_mfma_large_f32(A, E, stream);
+        if (rc == -5) return CS_NEED_MAP;
+        if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (sink) ctx->cand_fused = true;
         return CS_OK;
     }
     if (!A.out.ptr) return CS_NEED_MAP;      // every other kernel writes a map
@@ -1081,6 +1173,7 @@ void cs_ctx_destroy(cs_ctx* ctx)
     if (ctx->d_wfrag) (void)hipFree(ctx->d_wfrag);
     if (ctx->d_rim) (void)hipFree(ctx->d_rim);
     if (ctx->d_wfrag_wide) (void)hipFree(ctx->d_wfrag_wide);
+    if (ctx->d_wfrag_large) (void)hipFree(ctx->d_wfrag_large);
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
     if (ctx->d_cand_cnt) (void)hipFree(ctx->d_cand_cnt);
     if (ctx->d_map) (void)hipFree(ctx->d_map);

@@ -610,7 +610,8 @@ int cs_csr_tile_occupancy(cs_ctx* ctx, void* stream_, const cs_csr* mat, int32_t
     int rc = csr_view(ctx, mat, &v);
     if (rc) return rc;
     if (!n_tiles || cap < 0 || (cap > 0 && !d_tiles)) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
-    if (km <= 0 || kn <= 0 || !(km & 1) || !(kn & 1) || km > 65 || kn > 65) return fail(ctx, CS_ERR_INVALID, "bad template shape");
+    // (up to 81 x 81: the `centromeres` template, whose windows reach up to 3 x 3 tiles -- the marking loop walks however many)
+    if (km <= 0 || kn <= 0 || !(km & 1) || !(kn & 1) || km > 81 || kn > 81) return fail(ctx, CS_ERR_INVALID, "bad template shape");
     if (row_begin < 0 || row_end < row_begin || v.n_cols <= 0) return fail(ctx, CS_ERR_INVALID, "bad tile grid");
     *n_tiles = 0;
     const long long n = ((long long)v.n_cols + 63) / 64 * (((long long)row_end - row_begin + 63) / 64);

@@ -122,6 +122,12 @@ struct cs_ctx {
     std::vector<unsigned char> wfrag_wide_key;
     int wfrag_wide_km = 0, wfrag_wide_kn = 0;
     float wfrag_wide_unscale[3] = {1.0f, 1.0f, 1.0f};
+    // ... and for the kernel of the templates of 34 .. 81 (cs_launch.h MfmaLargeWeights)
+    void* d_wfrag_large = nullptr;
+    size_t d_wfrag_large_bytes = 0;
+    std::vector<unsigned char> wfrag_large_key;
+    int wfrag_large_km = 0, wfrag_large_kn = 0;
+    float wfrag_large_unscale[3] = {1.0f, 1.0f, 1.0f};
     int last_kernel = 0;     // cs_last_kernel()
     int range_check = 0;     // cs_ctx_set_range_check()
     bool cand_fused = false; // the last candidate-mode call appended its candidates itself (no map was written)

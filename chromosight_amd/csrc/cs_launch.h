@@ -74,4 +74,16 @@ struct MfmaWideWeights {
 bool corr_mfma_wide_fits(int km, int kn);
 int launch_corr_mfma_wide_f32(CorrArgs<float>& A, const MfmaWideWeights& E, hipStream_t s);
 
+// matrix-core kernel for templates with a side of 34 .. 81 (cs_corr_large.hip): `passes` = corr_mfma_large_passes(kn) k = 32
+// Toeplitz passes per template row.  frag[set][s][pass][head | tail][lane] = 8 float16 values
+// W_set[s][32 pass + 8 (lane >> 4) + e - (lane & 15)] * 2^ew (0 outside 0 .. kn-1), unscale[set] = 2^-ew.
+struct MfmaLargeWeights {
+    const uint4* frag;
+    float unscale[3];
+    int passes;
+};
+bool corr_mfma_large_fits(int km, int kn);
+int corr_mfma_large_passes(int kn);
+int launch_corr_mfma_large_f32(CorrArgs<float>& A, const MfmaLargeWeights& E, hipStream_t s);
+
 }  // namespace cs

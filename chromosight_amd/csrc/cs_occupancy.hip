@@ -6,7 +6,7 @@
 // candidates if its windows, dilated by the template, reach such a pixel.  Here:
 //
 //   occ_mark_kernel     one wave per CSR row of the view: every pixel with count > 0 and finite weights sets the bits of
-//                       the (at most 2 x 2, templates up to 65) output tiles whose windows reach it -- integer atomicOr only
+//                       the (at most 2 x 2 up to 65, 3 x 3 up to 81) output tiles whose windows reach it -- integer atomicOr only
 //   occ_compact_kernel  one workgroup: per 32-bit word a popcount, an exclusive scan in word order, and the set bits
 //                       written as tile indices by * tiles_x + bx -- the list is in increasing order, the same every run
 //

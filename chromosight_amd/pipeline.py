@@ -1515,7 +1515,7 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
     cfg["min_dist"] = 0
     kernels = [np.asarray(k, dtype=np.float64) for k in cfg["kernels"]]
     km, kn = kernels[0].shape
-    max_dist = max(cfg["max_dist"] // dcool.binsize, 1)
+    max_dist = int(max(cfg["max_dist"] // dcool.binsize, 1))        # (a numpy integer from the positions: ctypes takes ints)
     largest = max(k.shape[0] for k in kernels)
     # chromosome of every position, once (the four bin lookups below share it); HicGenome.coords_to_bins
     # (contacts_map.py:404-450): -1 where the genome has no such bin
