@@ -428,6 +428,80 @@ int ensure_wfrag_large(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::Mfma
 
 bool fast_available(int km, int kn, int* K);
 
+// Rank-revealing factorisation of a km x kn float64 matrix by elimination with complete pivoting: M = sum_i u_i v_i^T with
+// u_i = R[:, q] / R[p, q] (|u_i| <= 1) and v_i = R[p, :], R the residual and (p, q) its largest entry.  Returns the rank, or -1 when
+// more than max_rank terms are needed or the factors do not rebuild M to 1e-12 of its largest entry (the rank-1 check of
+// build_args, extended).  U: rank rows of km, V: rank rows of kn.
+int factor_low_rank(const double* M, int km, int kn, int max_rank, std::vector<double>& U, std::vector<double>& V)
+{
+    const int kk = km * kn;
+    std::vector<double> R(M, M + kk);
+    double mmax = 0;
+    for (int t = 0; t < kk; ++t) mmax = std::max(mmax, std::fabs(M[t]));
+    U.clear();
+    V.clear();
+    if (!(mmax > 0) || !std::isfinite(mmax)) return -1;
+    int rank = 0;
+    for (;; ++rank) {
+        int p = 0, q = 0;
+        double best = 0;
+        for (int t = 0; t < kk; ++t)
+            if (std::fabs(R[t]) > best) {
+                best = std::fabs(R[t]);
+                p = t / kn;
+                q = t - p * kn;
+            }
+        if (best <= 1e-13 * mmax) break;
+        if (rank == max_rank) return -1;
+        const double piv = R[(size_t)p * kn + q];
+        const size_t u0 = U.size(), v0 = V.size();
+        for (int a = 0; a < km; ++a) U.push_back(R[(size_t)a * kn + q] / piv);
+        for (int b = 0; b < kn; ++b) V.push_back(R[(size_t)p * kn + b]);
+        for (int a = 0; a < km; ++a)
+            for (int b = 0; b < kn; ++b) R[(size_t)a * kn + b] -= U[u0 + a] * V[v0 + b];
+    }
+    if (rank == 0) return -1;
+    double worst = 0;
+    for (int a = 0; a < km; ++a)
+        for (int b = 0; b < kn; ++b) {
+            double x = 0;
+            for (int i = 0; i < rank; ++i) x += U[(size_t)i * km + a] * V[(size_t)i * kn + b];
+            worst = std::max(worst, std::fabs(x - M[(size_t)a * kn + b]));
+        }
+    return worst <= 1e-12 * mmax ? rank : -1;
+}
+
+// the factor table of cs_corr_lowrank.hip, appended to a weight vector: 1 + ra + rb rows of kn row weights [1, va_j, vb_k], then as
+// many rows of km column weights [1, ua_j, ub_k] (Wa = sum_j ua_j va_j^T, Wb = sum_k ub_k vb_k^T)
+void append_lowrank_table(std::vector<double>& w, int km, int kn, const std::vector<double>& UA, const std::vector<double>& VA, int ra,
+                          const std::vector<double>& UB, const std::vector<double>& VB, int rb)
+{
+    w.insert(w.end(), (size_t)kn, 1.0);
+    w.insert(w.end(), VA.begin(), VA.begin() + (size_t)ra * kn);
+    w.insert(w.end(), VB.begin(), VB.begin() + (size_t)rb * kn);
+    w.insert(w.end(), (size_t)km, 1.0);
+    w.insert(w.end(), UA.begin(), UA.begin() + (size_t)ra * km);
+    w.insert(w.end(), UB.begin(), UB.begin() + (size_t)rb * km);
+}
+
+// Which float32 calls take the separable kernel of truncated-SVD templates (cs_corr_lowrank.hip): templates whose factors
+// build_args cached (--tsvd) -- and plain cross-correlations, which carry no tsvd marker, only under the forced setting.
+// CHROMOSIGHT_HIP_LOWRANK=1: every such call the kernel supports; =0: none (the kernels of the full template).  Unset: where it
+// was measured faster (tools/prof_lowrank.py, profiles/lowrank_time.json, loops resized, rank 2 / 2).  Map calls with a side of
+// 34 .. 81, which the runtime-size kernel serves otherwise: dense 4096^2 4.0x at 41, 4.8x at 61; C4' band with per-bin masks 1.3x at
+// 41, 1.8x at 61.  Candidate sinks with a side of 34 .. 41: on the C4' band 1.03x the matrix-core kernel of cs_corr_large.hip at 41,
+// 0.63x at 61.  The matrix-core kernels of up to 33 x 33 stay ahead on every shape measured (loops / borders 17, stripes 31, loops 33).
+bool lowrank_wanted(const cs::CorrArgs<float>& A)
+{
+    if (A.w_lr <= 0 || !cs::corr_lowrank_supports(A)) return false;
+    const char* e = std::getenv("CHROMOSIGHT_HIP_LOWRANK");
+    if (e && e[0] == '0') return false;
+    if (e && e[0] == '1') return true;
+    const int side = std::max(A.km, A.kn);
+    if (side < 34 || (A.w_lr + A.w_lr2 + 2) * (A.km + A.kn) * 2 > A.km * A.kn) return false;
+    return A.out.ptr ? true : side <= 41;
+}
+
 // Which float32 calls take the two-pass matrix-core kernel (cs_corr_wide.hip): templates with a side of 18 .. 33 -- what
 // `--win-size` makes (cli/chromosight.py:365-370) and the 19 x 19 .. 33 x 33 templates of API users -- in every container
 // the runtime-size kernel served (bands and dense maps, float32 and float64, any mask, n_obs, plain cross-correlations).
@@ -701,6 +775,16 @@ int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, 
     A.n_cu = ctx->n_cu;
     A.grid_cap = ctx->grid_cap;
     A.reg_mode = 0;
+    // truncated-SVD templates of low rank: row and column passes (maps; a layout or call form the kernel does not take returns -5 / -6
+    // before anything is launched, and the call goes on below)
+    if (allow_fast && lowrank_wanted(A)) {
+        rc = cs::launch_corr_lowrank_f32(A, stream);
+        if (rc == 0) {
+            ctx->last_kernel = CS_KERNEL_LOWRANK;
+            return CS_OK;
+        }
+        if (rc != -3 && rc != -5 && rc != -6) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
     // per-bin masks on the matrix cores: the factorised mask tables + the persistent tile kernel
     // (candidate mode without a sink -- the map fallback of find_candidates -- runs on the kernels that decide the screen
     // at run time: the tile kernel's candidate instance has no map output)
@@ -1014,6 +1098,30 @@ int build_args(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const c
                     }
                 }
             }
+            // --tsvd (h_kernel_sq set): K' and Q' are exact rank-r products by construction.  Up to rank 8 the float32 weight sets
+            // Wa (= K' - mean) and Wb are factored themselves for the separable kernel (cs_corr_lowrank.hip), behind the three sets: it
+            // then forms the very sums the full-template kernels form, none as a difference of larger ones
+            tc.lr = tc.lr2 = tc.lra = tc.lrb = 0;
+            if (sizeof(TC) == 4 && kernel->h_kernel_sq) {
+                // (the sets as build_args forms them above, before the symmetrisation of rounding-level asymmetries)
+                std::vector<double> U, V, UA, VA, UB, VB, wa(kk), wb(kk);
+                for (int t = 0; t < kk; ++t) {
+                    const double kc = kconv[t], k2 = kernel->h_kernel_sq[t];
+                    wa[t] = kc - st0.kmean;
+                    wb[t] = k2 - 2.0 * st0.kmean * kc + st0.kmean * st0.kmean;
+                }
+                const int r = factor_low_rank(kconv, km, kn, 8, U, V);
+                const int r2 = r > 0 ? factor_low_rank(kernel->h_kernel_sq, km, kn, 8, U, V) : -1;
+                const int ra = r2 > 0 ? factor_low_rank(wa.data(), km, kn, r + 1, UA, VA) : -1;
+                const int rb = ra > 0 ? factor_low_rank(wb.data(), km, kn, r + r2 + 1, UB, VB) : -1;
+                if (rb > 0) {
+                    append_lowrank_table(w0, km, kn, UA, VA, ra, UB, VB, rb);
+                    tc.lr = r;
+                    tc.lr2 = r2;
+                    tc.lra = ra;
+                    tc.lrb = rb;
+                }
+            }
             // can sum_missing K' or sum_missing K'^2 of a non-empty set fall under the zeroing threshold?
             // not if every entry alone exceeds it and all have one sign (the built-in templates: >= 0.5)
             double lo = 1e300, lo2 = 1e300;
@@ -1084,6 +1192,10 @@ int build_args(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const c
     A.xcorr_only = 0;
     A.w_sym = sym ? 1 : 0;
     A.w_rank1 = tc.rank1 ? 1 : 0;
+    A.w_lr = tc.lr;
+    A.w_lr2 = tc.lr2;
+    A.w_lrc = tc.lra;
+    A.w_lrb = tc.lrb;
     A.row_begin = 0;
     A.row_end = p->ms;
     if (p->row_end > p->row_begin) {

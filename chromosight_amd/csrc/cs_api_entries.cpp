@@ -274,6 +274,16 @@ int cs_xcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, int32_t ms, i
                 sym = false;
                 break;
             }
+    // plain cross-correlations carry no tsvd marker: the separable kernel of low-rank templates takes them only when forced
+    // (CHROMOSIGHT_HIP_LOWRANK=1), with the factors of the weights as passed
+    int lr = 0;
+    const char* lr_env = getenv("CHROMOSIGHT_HIP_LOWRANK");
+    if (compute_dtype == CS_F32 && lr_env && lr_env[0] == '1') {
+        std::vector<double> U, V, none;
+        lr = factor_low_rank(h_weights, km, kn, 8, U, V);
+        if (lr > 0) append_lowrank_table(w, km, kn, U, V, lr, none, none, 0);
+        else lr = 0;
+    }
 #define CS_XC(TC)                                                         \
     {                                                                     \
         rc = upload_weights<TC>(ctx, stream, w);                          \
@@ -291,6 +301,8 @@ int cs_xcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, int32_t ms, i
         A.ks.n = (TC)kk; A.ks.thr = (TC)threshold;                        \
         A.xcorr_only = 1;                                                 \
         A.w_sym = sym ? 1 : 0;                                            \
+        A.w_lr = A.w_lrc = sizeof(TC) == 4 ? lr : 0;                      \
+        A.w_lrb = 0;                                                      \
         return launch_corr<TC>(ctx, A, stream, getenv("CHROMOSIGHT_HIP_FORCE_GENERIC") == nullptr); \
     }
     if (compute_dtype == CS_F64) CS_XC(double)

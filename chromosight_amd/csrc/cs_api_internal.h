@@ -145,6 +145,8 @@ struct cs_ctx {
         std::vector<double> w;
         bool sym = false;
         bool rank1 = false;           // template == u v^T exactly: u, v appended to w (float32 kernels)
+        int lr = 0, lr2 = 0, lra = 0, lrb = 0;  // --tsvd: ranks of K', Q' and of the weight sets Wa, Wb, whose factor table is appended
+                                                // to w (float32, cs_corr_lowrank.hip)
         int zk_possible = 1, snap_possible = 1;
     } tcache[2];
     long long* h_blk_counts = nullptr;     // page-locked: total + per-block foci counts of cs_detect_foci_batch
@@ -331,6 +333,11 @@ int upload_weights(cs_ctx* ctx, hipStream_t stream, const std::vector<double>& w
 extern template int upload_weights<float>(cs_ctx*, hipStream_t, const std::vector<double>&);
 extern template int upload_weights<double>(cs_ctx*, hipStream_t, const std::vector<double>&);
 int ensure_wfrag(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWeights* E);
+// low-rank factors (cs_api.cpp): rank-revealing factorisation of a float64 matrix (rank <= max_rank, else -1) and the factor table
+// of cs_corr_lowrank.hip appended to a weight vector
+int factor_low_rank(const double* M, int km, int kn, int max_rank, std::vector<double>& U, std::vector<double>& V);
+void append_lowrank_table(std::vector<double>& w, int km, int kn, const std::vector<double>& UA, const std::vector<double>& VA, int ra,
+                          const std::vector<double>& UB, const std::vector<double>& VB, int rb);
 // kernel dispatch of one correlation call (cs_api.cpp).  CS_NEED_MAP: a candidate sink was given without a map, and the kernel
 // that would serve the call writes maps (nothing was launched that matters: the caller allocates the map and calls again)
 constexpr int CS_NEED_MAP = 1000;

@@ -218,6 +218,9 @@ struct CorrArgs {
     int grid_cap;            // > 0: at most this many persistent workgroups (tile kernel launches that run side by side)
     int w_sym;               // all three weight sets are symmetric under a vertical flip (row s == row km-1-s)
     int w_rank1;             // the template is exactly u v^T: u (km values) and v (kn) follow the three weight sets in `w`
+    int w_lr, w_lr2;         // > 0: truncated-SVD template of rank w_lr (K') and w_lr2 (its squares' Q'): the factor table of
+                             // cs_corr_lowrank.hip follows the three weight sets in `w` (float32 only)
+    int w_lrc, w_lrb;        // ranks of the factors in that table: Wa = K' - mean (plain xcorr2: the weights as passed) and Wb
     // factorised per-bin mask sums of the streaming kernel (cs_mask_prep.hip); reg_mode = 1:
     // strips whose windows stay inside the matrix use the tables, the others the general path
     int reg_mode;

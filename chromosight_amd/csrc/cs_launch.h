@@ -25,6 +25,9 @@ void corr_generic_tile(int km, int kn, int* tw, int* th);
 int launch_corr_sep_f32(const CorrArgs<float>& A, hipStream_t s);
 bool corr_sep_fits(int km, int kn, bool masked);
 void corr_sep_tile(int* tw, int* th);
+// separable evaluation of truncated-SVD templates of rank <= 8 (cs_corr_lowrank.hip): the factor table at A.w + 3 km kn
+bool corr_lowrank_supports(const CorrArgs<float>& A);
+int launch_corr_lowrank_f32(const CorrArgs<float>& A, hipStream_t s);
 
 // matrix-core kernel for templates up to 17 x 17, float32 class (cs_corr_mfma.hip).  The weight sets
 // arrive as ready-made B fragments: frag[set][s][head | tail][lane] = 8 float16 values
