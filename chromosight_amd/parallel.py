@@ -874,6 +874,91 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
 
 
 # ================================================================================================
+# `detect --inter`, sub-matrices (intra blocks, trans blocks in strips) sharded over the ranks
+# ================================================================================================
+def inter_unit_costs(pairs, sizes, max_dist, largest):
+    """Pixels of every (ca, cb) unit of `detect --inter` (pipeline.sub_matrices order), from the shapes alone: the band an
+    intra block scans, n * min(max_dist + largest, n), and the whole area n_r * n_c of a trans block (its strip fill, the
+    occupancy narrowing and the list kernel all scale with the area when few tiles are empty)."""
+    sizes = [int(n) for n in sizes]
+    return [sizes[a] * min(int(max_dist) + int(largest), sizes[a]) if a == b else sizes[a] * sizes[b] for a, b in pairs]
+
+
+class DetectShard:
+    """How pipeline.detect(inter=True) shares its sub-matrices among the ranks (detect_inter_genome): `select` keeps this
+    rank's units -- LPT (assign_blocks) over inter_unit_costs, the same lists on every rank --, `merge` all-gathers the
+    per-unit tables (and windows) after every template and iteration, so that every rank continues with the list the single
+    process builds: tables and windows of all units in sub_matrices order.
+
+    owned: this rank's unit indices, fixed by the caller (default: LPT).  exchange=False: nothing is merged, every rank keeps
+    its own units' tables (a share timed alone); only with single-iteration templates -- the next template of an iteration
+    is the pileup of ALL units' windows."""
+
+    def __init__(self, owned=None, exchange=True):
+        self.dist, self.rank, self.world = _world()
+        self.owned = None if owned is None else sorted(int(u) for u in owned)
+        self.exchange = bool(exchange)
+
+    def check(self, kernel_config):
+        """Argument checks (pipeline.detect runs them before any device work or collective)."""
+        if not self.exchange and kernel_config["max_iterations"] != 1:
+            raise ValueError("DetectShard(exchange=False) needs max_iterations == 1: an iteration's template is the pileup of all units")
+
+    def select(self, pairs, sizes, max_dist, largest):
+        if self.owned is not None:
+            if any(u < 0 or u >= len(pairs) for u in self.owned):
+                raise ValueError(f"DetectShard: owned units must be in 0 .. {len(pairs) - 1}")
+            return list(self.owned)
+        if self.world == 1:
+            return list(range(len(pairs)))
+        return assign_blocks(inter_unit_costs(pairs, sizes, max_dist, largest), self.world)[self.rank]
+
+    def merge(self, units, results, kernel_shape, need_windows):
+        """units: this rank's unit indices; results: their (table (k, 4) or None, windows (k, km, kn) or None).  Returns (unit
+        indices, results) of every unit of every rank that found something, in unit order -- ONE count exchange and ONE padded
+        all-gather of rows [unit, bin1, bin2, score, pvalue] (+ km * kn window values with need_windows), whatever this rank
+        holds."""
+        if not self.exchange or self.world == 1:
+            return units, results
+        kk = int(np.prod(kernel_shape)) if need_windows else 0
+        parts = []
+        for u, (tab, win) in zip(units, results):
+            if tab is None or len(tab) == 0:
+                continue
+            rec = np.empty((len(tab), 5 + kk))
+            rec[:, 0] = u
+            rec[:, 1:5] = tab
+            if kk:
+                rec[:, 5:] = np.asarray(win, dtype=np.float64).reshape(len(tab), kk)
+            parts.append(rec)
+        local = np.concatenate(parts, axis=0) if parts else np.zeros((0, 5 + kk))
+        import time
+        t0 = time.perf_counter()
+        merged = all_gather_rows(local)
+        TIMERS["exchange_ms"] += (time.perf_counter() - t0) * 1e3
+        TIMERS["exchanges"] += 1
+        # ranks concatenated; every unit comes from ONE rank with its rows in order: a stable sort by unit is the unit order
+        merged = merged[np.argsort(merged[:, 0], kind="stable")]
+        done, out = [], []
+        ids = merged[:, 0].astype(np.int64)
+        cuts = np.flatnonzero(np.diff(ids)) + 1
+        for rows in np.split(merged, cuts) if merged.shape[0] else []:
+            done.append(int(rows[0, 0]))
+            win = rows[:, 5:].reshape((rows.shape[0],) + tuple(kernel_shape)) if kk else None
+            out.append((np.ascontiguousarray(rows[:, 1:5]), win))
+        return done, out
+
+
+def detect_inter_genome(cool, kernel_config, **options):
+    """`chromosight detect --inter` with the sub-matrices sharded over the ranks like the reference's process pool
+    (cli/chromosight.py:738-755): every rank stages and scans its own intra blocks and its own trans blocks (in row strips of at
+    most inter_budget bytes), the per-unit tables are all-gathered after every template and iteration, and every rank returns
+    the table (with return_windows, also the windows) a single process returns.  Options: those of pipeline.detect."""
+    from . import pipeline
+    return pipeline.detect(cool, kernel_config, inter=True, shard=DetectShard(), **options)
+
+
+# ================================================================================================
 # `quantify`, sub-matrices sharded over the ranks
 # ================================================================================================
 class QuantifyShard:
@@ -881,15 +966,27 @@ class QuantifyShard:
     positions, coordinates) work list -- longest-processing-time-first by the pixels a sub-matrix stages plus the windows its
     positions read, the same list on every rank --, `merge` exchanges the scores once (one padded all-gather of
     (position, template, score, p-value, window) rows: RCCL with the "nccl" backend, gloo in the CPU tests)."""
+    prices_strips = True                      # (pipeline.quantify hands select the strip budget and the template reach)
 
     def __init__(self):
         self.dist, self.rank, self.world = _world()
 
-    def select(self, todo, dcool, max_dist):
+    def select(self, todo, dcool, max_dist, budget=None, reach=None):
+        """budget, reach: inter_budget and the largest template's side -- a trans sub-matrix is then priced by the rows its strips
+        stage (pipeline._row_groups, halo included) times its columns; without them by its whole area."""
+        from . import pipeline
         costs = []
-        for ca, cb, sel, _ in todo:
+        for ca, cb, sel, coords in todo:
             n_r, n_c = dcool.chrom_size(ca), dcool.chrom_size(cb)
-            staged = n_r * min(max_dist + 1, n_c) if ca == cb else n_r * n_c
+            if ca == cb:
+                staged = n_r * min(max_dist + 1, n_c)
+            elif budget is None or reach is None:
+                staged = n_r * n_c
+            else:
+                halo = (reach - 1) // 2
+                rows = np.unique(np.clip(np.asarray(coords, dtype=np.int64).reshape(-1, 2)[:, 0], 0, n_r - 1))
+                groups = pipeline._row_groups(rows, n_r, n_c, budget, halo)
+                staged = sum(hi - lo for lo, hi in (pipeline._strip_rows(n_r, g, halo) for g in groups)) * n_c
             costs.append(int(staged) + 512 * len(sel))
         owned = assign_blocks(costs, self.world)[self.rank]
         return [todo[i] for i in owned]

@@ -1365,7 +1365,7 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
 
 def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, inter=False, subsample=None, seed=0,
-           return_windows=False, win_size=None, inter_budget=None, sampler="numpy"):
+           return_windows=False, win_size=None, inter_budget=None, sampler="numpy", shard=None):
     """`chromosight detect` (balanced matrix) on a decoded cool (dict) or a DeviceCool; options
     --inter, --smooth-trend, --tsvd, --subsample (seeded), --iterations through the config.  Every
     block is staged once in HBM (distance law, detrend, band / median scaling) and stays resident
@@ -1374,9 +1374,16 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
     return_windows also the windows of its rows (what the reference saves as <prefix>.json / .npy).
     With inter, the trans blocks are not resident: each is scanned in row strips of at most inter_budget bytes
     (default INTER_BUDGET_DEFAULT) by detect_inter_block, one block at a time.
-    sampler: how --subsample draws, "numpy" (the host path) or "device" (DeviceCool.subsampled)."""
+    sampler: how --subsample draws, "numpy" (the host path) or "device" (DeviceCool.subsampled).
+    shard: parallel.DetectShard, with inter only -- the sub-matrices (intra blocks and trans blocks, in strips) are dealt to the
+    ranks, the per-block tables (and windows) are all-gathered after every template and iteration, and every rank returns
+    the single-process result (parallel.detect_inter_genome)."""
     budget = _check_budget(inter_budget)
     kernel_config = with_win_size(kernel_config, win_size)
+    if shard is not None:
+        if not inter:
+            raise ValueError("detect(shard=...) runs the --inter route only; intra-only sharding is parallel.detect_genome")
+        shard.check(kernel_config)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
     if subsample is not None:
         dcool = dcool.subsampled(subsample, seed=seed, inter=inter, sampler=sampler)
@@ -1402,13 +1409,16 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
                   "pvalue": rec[:, 4], "kernel_id": rec[:, 5].astype(np.int64), "iteration": rec[:, 6].astype(np.int64)}
         return postprocess(coords, kernel_config, binsize, off, names, dcool.bin_start, dcool.bin_end)
     pairs = sub_matrices(dcool, inter)
-    intra = dict(zip([a for a, b in pairs if a == b],
-                     dcool.stage_blocks([a for a, b in pairs if a == b], max_dist, largest, smooth=smooth, band_dtype=band_dtype)))
+    # this rank's sub-matrices (indices into pairs, in pairs order): all of them without a shard
+    units = list(range(len(pairs))) if shard is None else shard.select(pairs, np.diff(off), max_dist, largest)
+    own = [pairs[u] for u in units]
+    intra = dict(zip([a for a, b in own if a == b],
+                     dcool.stage_blocks([a for a, b in own if a == b], max_dist, largest, smooth=smooth, band_dtype=band_dtype)))
     # trans blocks: staged strip by strip for every template and iteration (detect_inter_block), scaled by their median
-    trans = [(a, b) for a, b in pairs if a != b]
+    trans = [(a, b) for a, b in own if a != b]
     medians = {pair: dcool.inter_median(*pair) for pair in trans}
     reach = _strip_reach(kernel_config["kernels"])
-    blocks = [intra[a] for a, b in pairs if a == b]
+    blocks = [intra[a] for a, b in own if a == b]
     all_coords, all_windows = [], []
     for kernel_id, kernel in enumerate(kernel_config["kernels"]):
         for it in range(kernel_config["max_iterations"]):
@@ -1419,8 +1429,13 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
             results = [next(cis) if a == b else
                        detect_inter_block(dcool, a, b, kernel_config, kernel, tsvd=tsvd, want_windows=need_windows, inter_budget=budget,
                                           reach=reach, median=medians[(a, b)])
-                       for a, b in pairs]
-            for (ca, cb), (tab, win) in zip(pairs, results):
+                       for a, b in own]
+            done = units
+            if shard is not None:
+                # every rank issues this exchange, whatever it owns or found: afterwards the tables (and windows) of ALL units, in
+                # pairs order -- the list the single process builds
+                done, results = shard.merge(units, results, np.shape(kernel), need_windows)
+            for (ca, cb), (tab, win) in zip([pairs[u] for u in done], results):
                 if tab is None or len(tab) == 0:
                     continue
                 tab[:, 0] += int(off[ca])
@@ -1450,7 +1465,9 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
 
 def detect_to_files(cool, kernel_config, prefix, win_fmt="json", dec=10, **options):
     """detect + the two files `chromosight detect` leaves behind (cli/chromosight.py:873-881):
-    <prefix>.tsv and <prefix>.json | .npy.  Returns the table."""
+    <prefix>.tsv and <prefix>.json | .npy.  Returns the table.  With shard=parallel.DetectShard() (and inter=True) under a
+    launcher, only rank 0 should call this -- two ranks would write the same files --, every other rank calls
+    parallel.detect_inter_genome with the same options (each rank takes part in every exchange)."""
     from . import io as cio
     cio.check_prefix_dir(prefix)
     table, windows = detect(cool, kernel_config, return_windows=True, **options)
@@ -1499,8 +1516,8 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
     last of each (chrom1, start1, chrom2, start2) group).  `positions`: DataFrame with chrom1, start1,
     end1, chrom2, start2, end2.  Returns (table in the reference's output order and columns, windows).
     shard: parallel.QuantifyShard -- the sub-matrices are dealt to the ranks (parallel.quantify_genome).
-    With inter (and no shard), a trans block is never staged whole: only the rows that hold a position, plus the halo, in
-    strips of at most inter_budget bytes (quantify_inter_block).  sampler: how --subsample draws, "numpy" or "device"
+    With inter (with a shard or without), a trans block is never staged whole: only the rows that hold a position, plus the
+    halo, in strips of at most inter_budget bytes (quantify_inter_block).  sampler: how --subsample draws, "numpy" or "device"
     (DeviceCool.subsampled)."""
     budget = _check_budget(inter_budget)
     dcool = cool if isinstance(cool, DeviceCool) else DeviceCool(cool)
@@ -1562,24 +1579,19 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
         todo.append((ca, cb, sel, np.column_stack([g1[sel] - dcool.offsets[ca], g2[sel] - dcool.offsets[cb]]).astype(int)))
     # Sharded run (parallel.quantify_genome): this rank scores the positions of its own sub-matrices, the scores of all ranks
     # are exchanged once below -- the reference's pool over sub-matrices (cli/chromosight.py:396-410)
-    mine = todo if shard is None else shard.select(todo, dcool, max_dist)
-    strips = [] if shard is not None else [t for t in mine if t[0] != t[1]]
-    if strips:
-        mine = [t for t in mine if t[0] == t[1]]
-    # every sub-matrix that holds a position is staged once: the intra blocks with ONE native call (cs_stage_blocks)
-    staged = {}
-    intra = sorted({ca for ca, cb, _, _ in mine if ca == cb})
-    if intra:
-        for ca, blk in zip(intra, dcool.stage_blocks(intra, max_dist, largest, smooth=smooth)):
-            staged[(ca, ca)] = blk
-    inter_pairs = [(ca, cb) for ca, cb, _, _ in mine if ca != cb]
-    if len(inter_pairs) > 1:
-        for pair, blk in zip(inter_pairs, dcool.stage_inter_many(inter_pairs)):
-            staged[pair] = blk
+    if shard is None:
+        mine = todo
+    elif getattr(shard, "prices_strips", False):         # (parallel.QuantifyShard: trans units priced by the rows they stage)
+        mine = shard.select(todo, dcool, max_dist, budget=budget, reach=_strip_reach(kernels))
     else:
-        for ca, cb in inter_pairs:
-            staged[(ca, cb)] = dcool.stage_inter(ca, cb, resident=True)
-    blocks = [staged[(ca, cb)] for ca, cb, _, _ in mine]
+        mine = shard.select(todo, dcool, max_dist)
+    # trans sub-matrices, with a shard or without: never staged whole, only the rows of their positions (quantify_inter_block)
+    strips = [t for t in mine if t[0] != t[1]]
+    mine = [t for t in mine if t[0] == t[1]]
+    # every intra sub-matrix that holds a position is staged once, with ONE native call (cs_stage_blocks)
+    intra = [ca for ca, _, _, _ in mine]
+    staged = dict(zip(intra, dcool.stage_blocks(intra, max_dist, largest, smooth=smooth))) if intra else {}
+    blocks = [staged[ca] for ca, _, _, _ in mine]
     # one native call per template for the positions of all sub-matrices (cs_quantify_blocks), the coordinate lists prepared
     # once for all templates ...
     res_all = None
@@ -1622,7 +1634,7 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
         dcool._strip_pool().release()
     if shard is not None:
         win_out = [win_array(k) for k in range(len(kernels))]
-        score_out, pval_out, win_out = shard.merge(score_out, pval_out, win_out, [sel for _, _, sel, _ in mine])
+        score_out, pval_out, win_out = shard.merge(score_out, pval_out, win_out, [sel for _, _, sel, _ in mine + strips])
     # best score of every coordinate among the templates, as the reference selects it (:432-441): the tables of the templates
     # one below the other, sort_values("score"), last row of every (chrom1, start1, chrom2, start2) group.  In numpy -- the
     # same argsort pandas runs (quicksort on the finite scores, NaN last), so ties fall as they do there -- because the

@@ -59,6 +59,12 @@ def occupancy_brute(dense_ok, km, kn, row_begin, row_end):
     return np.array(out, dtype=np.int64)
 
 
+def trans_chrom_sizes(total_bins=310_000, n_chroms=24):
+    """Chromosome sizes in bins of make_trans_cool's default genome: hg38 proportions, chrX last, chrY small."""
+    mb = np.asarray(list(np.asarray(genome_sizes(1_000_000))[:23]) + [57 * 1_000_000 / 3_100], dtype=np.float64)[:n_chroms]
+    return np.maximum((mb / mb.sum() * total_bins).astype(np.int64), 256)
+
+
 def make_trans_cool(total_bins=310_000, n_chroms=24, intra_diags=200, n_trans=20_000_000, n_planted=40, template=None, binsize=10_000,
                     seed=5, chrom_sizes=None):
     """Decoded-.cool dictionary: chromosomes in hg38 proportions (chrX last, chrY small), an intra band of `intra_diags`
@@ -67,8 +73,7 @@ def make_trans_cool(total_bins=310_000, n_chroms=24, intra_diags=200, n_trans=20
     with 1 % missing bins.  Returns (cool, planted [(bin1, bin2)] genome-wide)."""
     rng = np.random.default_rng(seed)
     if chrom_sizes is None:
-        mb = np.asarray(list(np.asarray(genome_sizes(1_000_000))[:23]) + [57 * 1_000_000 / 3_100], dtype=np.float64)[:n_chroms]
-        chrom_sizes = np.maximum((mb / mb.sum() * total_bins).astype(np.int64), 256)
+        chrom_sizes = trans_chrom_sizes(total_bins, n_chroms)
     sizes = np.asarray(chrom_sizes, dtype=np.int64)
     off = np.concatenate([[0], np.cumsum(sizes)])
     n = int(off[-1])
