@@ -462,6 +462,22 @@ __device__ __forceinline__ unsigned pack_h2(_Float16 a, _Float16 b)
     return __builtin_bit_cast(unsigned, v);
 }
 
+// x - (float) of the low / high float16 of h, exactly, in one instruction (v_fma_mix_f32 converts the half itself; the
+// compiler emits v_cvt_f32_f16 + v_sub_f32): the tail of a head + tail split
+__device__ __forceinline__ float sub_f16_lo(float x, unsigned h)
+{
+    float r;
+    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+    return r;
+}
+
+__device__ __forceinline__ float sub_f16_hi(float x, unsigned h)
+{
+    float r;
+    asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x));
+    return r;
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0): with
 // global stores or LDS-DMA transfers in flight it would stall every wave for a full memory round trip.
 __device__ __forceinline__ void lds_barrier()

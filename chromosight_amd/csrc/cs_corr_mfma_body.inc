@@ -174,6 +174,26 @@
         }
         const __attribute__((address_space(3))) char* dst =
             (const __attribute__((address_space(3))) char*)(raw) + (VEC4 ? 1024 : 256) * wv_u;
+        if constexpr (!REG && VEC4) {
+            // Inner tiles of a dense map (every staged row and column exists: nearly all of them): no clamp can bite, a
+            // piece's address is one base + r ld + 4 c -- the band instances' form below, without the diagonal shift.
+            if (P0 >= p_min && P0 + MF_R - 1 <= p_max && Q0 >= 0 && Q0 + MF_R <= FA->ns) {
+                const float* src = FA->sig + ((long long)P0 + r - FA->row0_in) * FA->ld_in + Q0 + 4 * c;
+                const long long step_r = 12 * FA->ld_in + 64, wrap = FA->ld_in - 80;      // 256 pieces on: 12 rows and 16 pieces
+#pragma unroll 1
+                for (int i = wv_u; i < kTransfers; i += 4) {
+                    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                    dst += 4096;
+                    c += 16;
+                    src += step_r;
+                    if (c >= kPiecesPerRow) {
+                        c -= kPiecesPerRow;
+                        src += wrap;
+                    }
+                }
+                return;
+            }
+        }
         if constexpr (REG && VEC4) {
             // Inner tiles of a band (every staged row exists, every staged diagonal is stored: 13 of the 18 tiles of a strip at
             // 1001 diagonals): no clamp can bite, a piece's address is one base + r (ld - 1) + 4 c -- two additions per transfer
@@ -650,6 +670,44 @@
         const int i = I0 + wr0 + n;
         const long long o_idx = ((long long)i - A.row0_out) * A.ld_out + (J0 + 4 * g);
         f4 rv[4];
+        // Lean form on the tile-scaled sums.  unscale (2^-ex), u_s2 / unscale (32) and w_unscale are powers of two and the
+        // coefficient is scale-invariant: with S1, S2' = 32 S2, cw = acc w_unscale the true sums are s1 = S1 u, s2 = S2' u^2,
+        // cs = cw u (u = unscale), so A = s2 n - s1^2 = u^2 (S2 32n - S1^2) and r = cs rsq(A kvar) = cw rsq(A' kvar) -- the
+        // same operations on operands scaled by powers of two (the result may still differ in the last bits: v_rsq_f32 is
+        // an approximation, not promised to be invariant under 4^k).  The thresholds move to the tile's units instead (one scaling per tile): every
+        // decision (eps cut, the three 1e-4 tests) falls on the same pixels as long as the scaled thresholds are normal
+        // floats and no true-domain term (s1^2, s2 n, den2) can overflow; other tiles, plain xcorr2, candidate mode and any
+        // wave holding a near-threshold window take the literal per-pixel form below.
+        bool lean = !A.xcorr_only && !MFD_DBG(32) && !(MFD_NOMASK_KS.cand_cmin > 0.0f);
+        if (lean) {
+            const KernelStats<float>& KS = MFD_NOMASK_KS;
+            const float inv_u = __uint_as_float((254u << 23) - __float_as_uint(unscale));          // 2^ex, exact
+            const float t1 = KS.thr_n * inv_u;                          // |s1|, |c| >= thr_n
+            const float t2 = (t1 * inv_u) * 0.03125f;                   // s2 >= thr_n
+            const float td = (KS.den2_min * inv_u) * inv_u;             // den2 >= den2_min
+            // (scaled sums: |S1| < 2^16, 32 n S2 < 2^31, so every true-domain term -- s1^2, s2 n, den2 -- is below this)
+            const float top = (fmaxf(KS.kvar, 1.0f) * 4294967296.0f) * (unscale * unscale);
+            auto normal_or_0 = [](float x) { return x == 0.0f || (x >= 1.17549435e-38f && x <= 3.40282347e38f); };
+            lean = normal_or_0(t1) && normal_or_0(t2) && normal_or_0(td) && td > 0.0f && top <= 3.40282347e38f;
+            if (lean) {
+                const float n32 = 32.0f * KS.n, wu = A.w_unscale;
+                bool normal = true;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const float s1 = S1[c][v], s2 = S2[c][v], cw = acc[c][v] * wu;
+                        const float den2 = fmaf(s2, n32, -s1 * s1) * KS.kvar;
+                        float r = cw * __builtin_amdgcn_rsqf(den2);
+                        r = (den2 >= td) ? r : 0.0f;                    // denominator under eps, NaN -> 0
+                        rv[c][v] = __builtin_amdgcn_fmed3f(r, -1.0f, 1.0f);
+                        normal &= (int)(fabsf(s1) >= t1) & (int)(s2 >= t2) & (int)(fabsf(fmaf(KS.kmean, s1, cw)) >= t1);
+                    }
+                }
+                lean = !__builtin_amdgcn_ballot_w64(!normal);
+            }
+        }
+        if (!lean)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
 #pragma unroll
@@ -1008,10 +1066,19 @@
                     // heads by truncation, tails exact differences: head + tail carries 21-22 bits either way
                     const float a = xa[k] * scale, b = xb[k] * scale;
                     const hv2 hh = __builtin_amdgcn_cvt_pkrtz(a, b);
-                    const hv2 tt = __builtin_amdgcn_cvt_pkrtz(a - (float)hh[0], b - (float)hh[1]);
                     const float qa = (xa[k] * qscale) * a, qb = (xb[k] * qscale) * b;
                     const hv2 qh = __builtin_amdgcn_cvt_pkrtz(qa, qb);
-                    const hv2 qt = __builtin_amdgcn_cvt_pkrtz(qa - (float)qh[0], qb - (float)qh[1]);
+                    hv2 tt, qt;
+                    if constexpr (!REG) {
+                        // (the tails straight from the packed heads: one v_fma_mix_f32 per value instead of a convert and a
+                        // subtraction -- the same exact differences; the masked instances keep their statement order)
+                        const unsigned hu = __builtin_bit_cast(unsigned, hh), qu = __builtin_bit_cast(unsigned, qh);
+                        tt = __builtin_amdgcn_cvt_pkrtz(sub_f16_lo(a, hu), sub_f16_hi(b, hu));
+                        qt = __builtin_amdgcn_cvt_pkrtz(sub_f16_lo(qa, qu), sub_f16_hi(qb, qu));
+                    } else {
+                        tt = __builtin_amdgcn_cvt_pkrtz(a - (float)hh[0], b - (float)hh[1]);
+                        qt = __builtin_amdgcn_cvt_pkrtz(qa - (float)qh[0], qb - (float)qh[1]);
+                    }
                     const int o = (r * MF_R + 2 * c2) * 2;
                     *reinterpret_cast<hv2*>(pl_xh + o) = hh;
                     *reinterpret_cast<hv2*>(pl_xl + o) = tt;
@@ -1061,16 +1128,33 @@
                 // in as they are (slot e of group g = row rho(g, e)) against the all-ones Toeplitz operand with its
                 // rows permuted the same way (ones_p): no transposition through LDS.
                 h8 bh, bl;
+                typedef unsigned u4 __attribute__((ext_vector_type(4)));
+                u4 bhw, blw;
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb) {
                     f4 h = mfma16(cur[2 * rb], ones_b, zero4);
                     h = mfma16(cur[2 * rb + 1], ones_b, h);
+                    if constexpr (!REG) {
+                        // heads rounded to nearest two at a time (v_cvt_pk_f16_f32), tails by v_fma_mix_f32 from the packed
+                        // heads: the same values as the form below in half the instructions
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const _Float16 hh = (_Float16)h[v];
-                        bh[4 * rb + v] = hh;
-                        bl[4 * rb + v] = (_Float16)(h[v] - (float)hh);
+                        for (int pr = 0; pr < 2; ++pr) {
+                            const unsigned hp = pack_h2((_Float16)h[2 * pr], (_Float16)h[2 * pr + 1]);
+                            bhw[2 * rb + pr] = hp;
+                            blw[2 * rb + pr] = pack_h2((_Float16)sub_f16_lo(h[2 * pr], hp), (_Float16)sub_f16_hi(h[2 * pr + 1], hp));
+                        }
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) {
+                            const _Float16 hh = (_Float16)h[v];
+                            bh[4 * rb + v] = hh;
+                            bl[4 * rb + v] = (_Float16)(h[v] - (float)hh);
+                        }
                     }
+                }
+                if constexpr (!REG) {
+                    bh = __builtin_bit_cast(h8, bhw);
+                    bl = __builtin_bit_cast(h8, blw);
                 }
                 f4 sacc = mfma16(bh, ones_p, zero4);
                 sacc = mfma16(bl, ones_p, sacc);
