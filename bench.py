@@ -25,6 +25,12 @@ throughput is N * pixels * steps / max-over-ranks time.
 
 Prints ONE JSON line on rank 0.  `ms_per_step` is the wall time of one of the `--steps` timed steps.
 
+A plain run does what its headline figure needs and nothing else: set-up, warm-up, the timed steps, the dump if asked for,
+the line.  --full adds what is measured beside it, after the timed region: the clock probe (`gpu_state`), and with c2 the
+north-star C4' leg, templates above 17 x 17, C3 from CSR, the sharded genome, detect wall-clock, C5, C2 in float64, the
+PCIe-inclusive API call and the CPU baselines (--no-cpu-baseline keeps --full to the clock probe); with c4, the single
+steps, phases and `detect` runs after the timed steps.
+
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed -- the arrays a caller of the
 timed path receives -- as DIR/<name>.npy (float32 / float64; an output above its share of 48 MiB keeps a fixed, seeded
 sample of its rows).  The inputs are seeded: two builds run with the same arguments can be compared file by file.
@@ -56,7 +62,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c3k", "c4p", "c4", "c5"])
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the clock probe and every reported extra leg (CPU baselines, other workloads, sizes "
+                         "and precisions, wider templates); a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: the clock probe alone, none of the extra legs")
     ap.add_argument("--size", type=int, default=4096, help="c2 only: side of the dense map (default 4096)")
     ap.add_argument("--plan", action="store_true",
                     help="no GPU work: print the block -> rank assignment of the sharded C4 genome for --gpus N and exit")
@@ -569,9 +579,10 @@ class GenomeC4:
         return rec_l, rec_b
 
 
-def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup, outputs=None):
+def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup, outputs=None, extras=True):
     """Time `steps` passes of the sharded C4 genome; returns the summary dict (same on every rank).  `outputs` (a dict):
-    receives the record tables of the last timed step."""
+    receives the record tables of the last timed step.  extras=False: nothing after the timed steps (`per_rank`,
+    `single_steps_ms` and `detect_wallclock_c4` None)."""
     g = GenomeC4(args, rank, local_rank, world)
 
     def sync():
@@ -598,71 +609,72 @@ def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup, outpu
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the same steps one by one (each bracketed by the synchronisation of the timed region), outside the timed region: median, minimum
-    # and the list beside the mean -- a step that ends on host threads has modes (profiles/r05_genome_step_modes.txt), and the mean of
-    # eight steps does not say which one a box was in
-    singles = []
-    for _ in range(min(max(steps, 4), 16)):
-        sync()
-        t1 = time.perf_counter()
-        rec = g.step()
-        sync()
-        singles.append((time.perf_counter() - t1) * 1e3)
-    if dist is not None:
-        t = torch.tensor(singles, dtype=torch.float64, device=f"cuda:{local_rank}")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        singles = [float(x) for x in t.tolist()]
-    # per-rank phases, outside the timed region (a device synchronisation between staging and detection would cost the
-    # timed steps their overlap): staging until its kernels are done, detection without the exchanges, the exchanges
-    phases = []
-    for _ in range(3):
-        g.dcool.dev.sync()
-        g.parallel.TIMERS.update(exchange_ms=0.0, exchanges=0)
-        ta = time.perf_counter()
-        staged = g.parallel.stage_genome(g.dcool, [g.loops, g.borders], owned=g.mine)
-        g.dcool.dev.sync()
-        tb = time.perf_counter()
-        g.parallel.detect_patterns(g.dcool, [g.loops, g.borders], owned=g.mine, staged=staged)
-        g.dcool.dev.sync()
-        tc = time.perf_counter()
-        ex = g.parallel.TIMERS["exchange_ms"]
-        phases.append(((tb - ta) * 1e3, (tc - tb) * 1e3 - ex, ex))
-    mine = {"rank": rank, "blocks": len(g.mine), "stage_ms": round(min(p[0] for p in phases), 3),
-            "detect_ms": round(min(p[1] for p in phases), 3), "exchange_ms": round(min(p[2] for p in phases), 3)}
-    per_rank = [mine]
-    if dist is not None:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
     pixels = g.loop_pixels + g.border_pixels
-    detect_c4 = None
-    if world == 1:
-        # `chromosight detect` END TO END at genome scale (BASELINE.json's "detect wall-clock"), one pattern per run like the CLI:
-        # resident pixel table -> final table (staging, correlation, foci, acceptance rules, neighbour removal, min_dist,
-        # Benjamini-Hochberg q-values: pipeline.detect, the counterpart of cli/chromosight.py:601-878 without the file I/O)
-        from chromosight_amd import pipeline
-        detect_c4 = {}
-        import copy as _copy
-        import chromosight_amd.kernels as _ck
-        for name, cfg in (("loops", g.loops), ("borders", g.borders), ("hairpins", _copy.deepcopy(_ck.hairpins))):
-            for _ in range(2):
-                table = pipeline.detect(g.dcool, cfg)
-            times = []
-            for _ in range(7):
-                g.dcool.dev.sync()
-                t0 = time.perf_counter()
-                table = pipeline.detect(g.dcool, cfg)
-                times.append((time.perf_counter() - t0) * 1e3)
-            detect_c4[name] = {"ms": round(float(np.median(times)), 3), "min_ms": round(min(times), 3), "rows": int(len(table)),
-                               "templates": len(cfg["kernels"])}
-        detect_c4["input"] = ("the C4 genome (200 000 bins, 23 chromosomes), pixel table resident in HBM; median of 7 runs of "
-                              "pipeline.detect per pattern, final table included")
+    singles, per_rank, detect_c4 = [], None, None
+    if extras:
+        # the same steps one by one (each bracketed by the synchronisation of the timed region), outside the timed region: median, minimum
+        # and the list beside the mean -- a step that ends on host threads has modes (profiles/r05_genome_step_modes.txt), and the mean of
+        # eight steps does not say which one a box was in
+        for _ in range(min(max(steps, 4), 16)):
+            sync()
+            t1 = time.perf_counter()
+            rec = g.step()
+            sync()
+            singles.append((time.perf_counter() - t1) * 1e3)
+        if dist is not None:
+            t = torch.tensor(singles, dtype=torch.float64, device=f"cuda:{local_rank}")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            singles = [float(x) for x in t.tolist()]
+        # per-rank phases, outside the timed region (a device synchronisation between staging and detection would cost the
+        # timed steps their overlap): staging until its kernels are done, detection without the exchanges, the exchanges
+        phases = []
+        for _ in range(3):
+            g.dcool.dev.sync()
+            g.parallel.TIMERS.update(exchange_ms=0.0, exchanges=0)
+            ta = time.perf_counter()
+            staged = g.parallel.stage_genome(g.dcool, [g.loops, g.borders], owned=g.mine)
+            g.dcool.dev.sync()
+            tb = time.perf_counter()
+            g.parallel.detect_patterns(g.dcool, [g.loops, g.borders], owned=g.mine, staged=staged)
+            g.dcool.dev.sync()
+            tc = time.perf_counter()
+            ex = g.parallel.TIMERS["exchange_ms"]
+            phases.append(((tb - ta) * 1e3, (tc - tb) * 1e3 - ex, ex))
+        mine = {"rank": rank, "blocks": len(g.mine), "stage_ms": round(min(p[0] for p in phases), 3),
+                "detect_ms": round(min(p[1] for p in phases), 3), "exchange_ms": round(min(p[2] for p in phases), 3)}
+        per_rank = [mine]
+        if dist is not None:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
+        if world == 1:
+            # `chromosight detect` END TO END at genome scale (BASELINE.json's "detect wall-clock"), one pattern per run like the CLI:
+            # resident pixel table -> final table (staging, correlation, foci, acceptance rules, neighbour removal, min_dist,
+            # Benjamini-Hochberg q-values: pipeline.detect, the counterpart of cli/chromosight.py:601-878 without the file I/O)
+            from chromosight_amd import pipeline
+            detect_c4 = {}
+            import copy as _copy
+            import chromosight_amd.kernels as _ck
+            for name, cfg in (("loops", g.loops), ("borders", g.borders), ("hairpins", _copy.deepcopy(_ck.hairpins))):
+                for _ in range(2):
+                    table = pipeline.detect(g.dcool, cfg)
+                times = []
+                for _ in range(7):
+                    g.dcool.dev.sync()
+                    t0 = time.perf_counter()
+                    table = pipeline.detect(g.dcool, cfg)
+                    times.append((time.perf_counter() - t0) * 1e3)
+                detect_c4[name] = {"ms": round(float(np.median(times)), 3), "min_ms": round(min(times), 3), "rows": int(len(table)),
+                                   "templates": len(cfg["kernels"])}
+            detect_c4["input"] = ("the C4 genome (200 000 bins, 23 chromosomes), pixel table resident in HBM; median of 7 runs of "
+                                  "pipeline.detect per pattern, final table included")
     return {
         "detect_wallclock_c4": detect_c4,
         "transport": transport, "per_rank": per_rank,
         "value": round(pixels * steps / elapsed / 1e6, 1), "unit": "Mpixel/s", "ms_per_genome": round(elapsed / steps * 1e3, 2),
         "single_steps_ms": {"median": round(float(np.median(singles)), 3), "min": round(min(singles), 3), "max": round(max(singles), 3),
                             "steps": [round(x, 3) for x in singles],
-                            "note": "the same step timed one at a time (synchronised on both sides, max over ranks), outside the timed region"},
+                            "note": "the same step timed one at a time (synchronised on both sides, max over ranks), outside the timed region"}
+                           if singles else None,
         "n_gpus": world, "steps": steps, "scaling": "strong",
         "workload": "C4: 200000 bins in 23 blocks (hg38 proportions), 2 kb bins, max_dist 1000 bins, 2 % unbalanced bins, "
                     "planted loops, pixel table resident in HBM; per step and per pattern (loops, borders x3): band "
@@ -679,7 +691,7 @@ def time_genome(args, rank, local_rank, world, dist, torch, steps, warmup, outpu
 def run_c4(args, rank, local_rank, world, dist, torch):
     """C4 of BASELINE.md end to end, blocks sharded over the ranks (strong scaling)."""
     outputs = {} if args.dump_outputs else None
-    r = time_genome(args, rank, local_rank, world, dist, torch, args.steps, args.warmup, outputs)
+    r = time_genome(args, rank, local_rank, world, dist, torch, args.steps, args.warmup, outputs, extras=args.full)
     if rank == 0:
         dumped = {"dumped_outputs": dump_outputs(args.dump_outputs, outputs)} if outputs is not None else {}
         print(json.dumps(dict({
@@ -973,7 +985,9 @@ def main():
 
     # The headline line is complete at this point.  The legs below are reported extras that use more of the stack (the
     # RCCL exchange of the sharded genome has only ever run where several GPUs exist): if one of them hangs, every rank
-    # leaves through this timer and rank 0 still prints the line, with a note instead of the leg.
+    # leaves through this timer and rank 0 still prints the line, with a note instead of the leg.  They run with --full
+    # only, like the clock probe: a plain run prints the line as it is.
+    legs = args.full and not args.no_cpu_baseline
     head = {}
     if rank == 0:
         total_pixels = wl.pixels * args.steps * world
@@ -993,7 +1007,7 @@ def main():
         }
         if dumped is not None:
             head["dumped_outputs"] = dumped
-        if world == 1:
+        if world == 1 and args.full:
             head["gpu_state"] = gpu_state(wl.step, full_sync, CLOCKS_AT_START)
     extras = {}
 
@@ -1007,7 +1021,7 @@ def main():
         os._exit(0)
 
     watchdog = None
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and legs:
         import signal
         import threading
         watchdog = threading.Timer(EXTRAS_TIMEOUT_S, bail_out)
@@ -1021,7 +1035,7 @@ def main():
     # the north-star configuration next to the headline one, kernel only, at every N (each rank its own 200 000-bin
     # block: weak scaling like `value`): C4' = one 200 000-bin block, band to 1000 bins, masks, full mode
     c4p = None
-    if args.workload == "c2" and args.size == 4096 and not args.no_cpu_baseline:
+    if args.workload == "c2" and args.size == 4096 and legs:
         try:
             del wl.out_buf
             w4 = Workload("c4p", dev, rank, args.precision)
@@ -1058,7 +1072,7 @@ def main():
     # whose step is more than the correlation call -- staging kernels (law pass writing the band of counts, finish), mask tables,
     # tile kernel
     c3 = None
-    if args.workload == "c2" and args.size == 4096 and not args.no_cpu_baseline and world == 1:
+    if args.workload == "c2" and args.size == 4096 and legs and world == 1:
         try:
             w3 = Workload("c3", dev, rank, args.precision)
             prewarm(w3.step, full_sync, 0.1)
@@ -1083,7 +1097,7 @@ def main():
         extras["c3_from_csr"] = c3
 
     genome = None
-    if not args.no_cpu_baseline and args.workload == "c2":
+    if legs and args.workload == "c2":
         # the sharded end-to-end genome next to the kernel figure, at every N (strong scaling, records
         # gathered over RCCL): all ranks take part
         try:
@@ -1106,7 +1120,7 @@ def main():
             out["wide_templates"] = extras["wide_templates"]
         if genome is not None:
             out["sharded_genome"] = genome
-        if not args.no_cpu_baseline and world == 1:     # reported extras: rank 0 at N = 1 only
+        if legs and world == 1:     # reported extras: rank 0 at N = 1 only
             try:
                 out["detect_wallclock"] = detect_wallclock()
             except Exception as exc:

@@ -12,9 +12,9 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 cd "$root"
 
-bench() { timeout 600 python bench.py "$@" 2>/dev/null | tail -1; }
+bench() { timeout 600 python bench.py --full "$@" 2>/dev/null | tail -1; }
 
-# 1. bench lines (the default command first: it is what the driver runs)
+# 1. bench lines, each with its reported extras (--full); the default command first
 bench > "$out/bench_c2.json"
 bench --workload c3 --no-cpu-baseline > "$out/bench_c3.json"
 bench --workload c3k --no-cpu-baseline > "$out/bench_c3k.json"
@@ -23,48 +23,48 @@ bench --workload c4 --steps 40 --warmup 8 > "$out/bench_c4.json"
 bench --workload c5 --steps 10 --warmup 2 > "$out/bench_c5.json"
 bench --size 16384 --steps 10 --warmup 3 --no-cpu-baseline > "$out/bench_dense16384.json"
 bench --precision f64 --no-cpu-baseline > "$out/bench_c2_f64.json"
-CHROMOSIGHT_HIP_NO_MFMA=1 CHROMOSIGHT_HIP_NO_SYMMETRY=1 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c2_nosym.json"
+CHROMOSIGHT_HIP_NO_MFMA=1 CHROMOSIGHT_HIP_NO_SYMMETRY=1 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c2_nosym.json"
 # the packed-FMA streaming kernel on the workloads whose default is a matrix-core kernel (dense map; banded maps with
 # the mirrored 17 x 17 loops template)
-CHROMOSIGHT_HIP_NO_MFMA=1 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c2_stream.json"
-CHROMOSIGHT_HIP_MFMA_REG=0 python bench.py --workload c3k --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c3k_stream.json"
-CHROMOSIGHT_HIP_MFMA_REG=0 python bench.py --workload c4p --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c4p_stream.json"
+CHROMOSIGHT_HIP_NO_MFMA=1 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c2_stream.json"
+CHROMOSIGHT_HIP_MFMA_REG=0 python bench.py --full --workload c3k --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c3k_stream.json"
+CHROMOSIGHT_HIP_MFMA_REG=0 python bench.py --full --workload c4p --no-cpu-baseline 2>/dev/null | tail -1 > "$out/bench_c4p_stream.json"
 
 # 2. kernel traces of the same commands (c3 and c4 show the helper kernels: band extents, distance law,
 #    tiler, mask tables, compaction, sort, foci, re-scoring)
 for w in c2 c3 c3k c4p; do
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_$w" -o $w -- \
-      python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > "$out/trace_$w.log" 2>&1
+      python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > "$out/trace_$w.log" 2>&1
 done
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace_c4" -o c4 -- \
-    python bench.py --workload c4 --steps 3 --warmup 1 > "$out/trace_c4.log" 2>&1
+    python bench.py --full --workload c4 --steps 3 --warmup 1 > "$out/trace_c4.log" 2>&1
 
 # 3. HBM counters of the dominant kernel of the dense and the two banded workloads, one pass each
 for w in c2 c3k c4p; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out/pmc_${w}_$c" -o $w -- \
-        python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_${w}_$c.log" 2>&1
+        python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_${w}_$c.log" 2>&1
   done
   # VALU / wave counters (own pass)
   timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY \
       --kernel-trace --output-format csv -d "$out/pmc_${w}_sq" -o $w -- \
-      python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_${w}_sq.log" 2>&1
+      python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_${w}_sq.log" 2>&1
 done
 # matrix-core occupancy of the dense kernel (own pass)
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
     --kernel-trace --output-format csv -d "$out/pmc_c2_mfma" -o c2 -- \
-    python bench.py --workload c2 --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c2_mfma.log" 2>&1
+    python bench.py --full --workload c2 --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c2_mfma.log" 2>&1
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
     --kernel-trace --output-format csv -d "$out/pmc_c4p_mfma" -o c4p -- \
-    python bench.py --workload c4p --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c4p_mfma.log" 2>&1
+    python bench.py --full --workload c4p --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c4p_mfma.log" 2>&1
 # the candidate (CAND) instances the pipeline runs -- corr_mfma_dense_kernel<.., CAND> per block, corr_mfma_blocks_kernel for
 # a rank's share -- on the C4 genome: matrix-core occupancy and HBM bytes (own passes)
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU \
     --kernel-trace --output-format csv -d "$out/pmc_c4_mfma" -o c4 -- \
-    python bench.py --workload c4 --steps 3 --warmup 1 > "$out/pmc_c4_mfma.log" 2>&1
+    python bench.py --full --workload c4 --steps 3 --warmup 1 > "$out/pmc_c4_mfma.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out/pmc_c4_$c" -o c4 -- \
-      python bench.py --workload c4 --steps 3 --warmup 1 > "$out/pmc_c4_$c.log" 2>&1
+      python bench.py --full --workload c4 --steps 3 --warmup 1 > "$out/pmc_c4_$c.log" 2>&1
 done
 timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU \
     --kernel-trace --output-format csv -d "$out/pmc_share_mfma" -o share -- \
@@ -91,7 +91,7 @@ bash tools/c4_mode_sweep.sh "$out/c4_modes.txt" > /dev/null 2>&1
 # helper kernels of the CSR path: bytes moved by the distance law / tiler (c3)
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$out/pmc_c3_$c" -o c3 -- \
-      python bench.py --workload c3 --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c3_$c.log" 2>&1
+      python bench.py --full --workload c3 --steps 5 --warmup 2 --no-cpu-baseline > "$out/pmc_c3_$c.log" 2>&1
 done
 
 # 4. FETCH_SIZE calibration on a known byte count with the kernel's own load pattern, and the
