@@ -4,6 +4,8 @@
 // declarations: cs_api_internal.h.  No torch types, no retained pointers.
 #include "cs_api_internal.h"
 
+extern char** environ;
+
 namespace csapi {
 
 // cs_stream_wait_tiles: one wave that sleeps until the word has reached `epoch` (the tile workgroups of the launch that carries this
@@ -179,47 +181,90 @@ float f16_bits_to_f32(uint16_t h)
     return out;
 }
 
-// Build (or reuse) the fragment image of the float32 weights currently in ctx->d_w[0] (layout in
-// cs_launch.h MfmaWeights).  Each set is scaled by the power of two that puts its largest magnitude in
-// [64, 128), so that heads and tails stay in float16's normal range.
-int ensure_wfrag(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWeights* E)
+// The float32 weight sets currently in ctx->d_w[0] (their host copy is the key of every image built from them): how many of the
+// three are there for a km x kn template
+static int cached_weight_sets(cs_ctx* ctx, int km, int kn, int* nsets)
 {
-    const std::vector<unsigned char>& key = ctx->w_cached[0];
     const int kk = km * kn;
-    const size_t n_floats = key.size() / 4;
+    const size_t n_floats = ctx->w_cached[0].size() / 4;
     if (kk <= 0 || n_floats < (size_t)kk) return fail(ctx, CS_ERR_INVALID, "weights missing for the matrix-core kernel");
-    if (km > 17 || kn > 17) return fail(ctx, CS_ERR_INVALID, "the matrix-core weight image holds templates of up to 17 x 17");
-    const int nsets = (int)std::min<size_t>(3, n_floats / kk);
-    constexpr size_t kImage = 3 * 17 * 2 * 1024;
-    if (!ctx->d_wfrag) CS_HIP(ctx, hipMalloc(&ctx->d_wfrag, kImage));
-    if (!(ctx->wfrag_km == km && ctx->wfrag_kn == kn && ctx->wfrag_key == key)) {
-        const float* w = reinterpret_cast<const float*>(key.data());
-        std::vector<uint16_t> img(kImage / 2, 0);
-        for (int set = 0; set < nsets; ++set) {
-            float amax = 0.0f;
-            for (int t = 0; t < kk; ++t) amax = std::max(amax, std::fabs(w[set * kk + t]));
-            int ew = 0;
-            if (amax > 0.0f && std::isfinite(amax)) {
-                int e2;
-                (void)std::frexp(amax, &e2);          // amax = f * 2^e2, f in [0.5, 1)
-                ew = 7 - e2;                           // amax * 2^ew in [64, 128)
-            }
-            ew = std::max(-100, std::min(100, ew));
-            ctx->wfrag_unscale[set] = std::ldexp(1.0f, -ew);
-            for (int s = 0; s < km; ++s)
+    *nsets = (int)std::min<size_t>(3, n_floats / kk);
+    return CS_OK;
+}
+
+// grow-only: a larger image replaces the old one, whose key is dropped
+static int ensure_image(cs_ctx* ctx, WeightImage& img, size_t bytes)
+{
+    if (bytes <= img.bytes) return CS_OK;
+    if (img.d) {
+        CS_HIP(ctx, hipDeviceSynchronize());   // a queued kernel may still read the old image
+        CS_HIP(ctx, hipFree(img.d));
+    }
+    img.d = nullptr;
+    img.bytes = 0;
+    img.key.clear();
+    CS_HIP(ctx, hipMalloc(&img.d, bytes));
+    img.bytes = bytes;
+    return CS_OK;
+}
+
+// the power of two that puts the largest magnitude of a weight set in [64, 128), so that heads and tails stay in float16's normal range
+static int weight_scale_exponent(const float* w, int kk)
+{
+    float amax = 0.0f;
+    for (int t = 0; t < kk; ++t) amax = std::max(amax, std::fabs(w[t]));
+    int ew = 0;
+    if (amax > 0.0f && std::isfinite(amax)) {
+        int e2;
+        (void)std::frexp(amax, &e2);          // amax = f * 2^e2, f in [0.5, 1)
+        ew = 7 - e2;                           // amax * 2^ew in [64, 128)
+    }
+    return std::max(-100, std::min(100, ew));
+}
+
+// The Toeplitz fragments of the first nsets weight sets, `passes` k = 32 passes per template row (the layouts of cs_launch.h):
+// halfs[(((set * km + s) * passes + pass) * 2 + {head, tail}) * 512 + 8 lane + e] = W_set[s][32 pass + 8 (lane >> 4) + e - (lane & 15)]
+// * 2^ew, 0 outside 0 .. kn-1 (halfs arrives zeroed); img.unscale[set] = 2^-ew
+static void pack_weight_sets(WeightImage& img, const float* w, int nsets, int km, int kn, int passes, uint16_t* halfs)
+{
+    const int kk = km * kn;
+    for (int set = 0; set < nsets; ++set) {
+        const int ew = weight_scale_exponent(w + set * kk, kk);
+        img.unscale[set] = std::ldexp(1.0f, -ew);
+        for (int s = 0; s < km; ++s)
+            for (int pass = 0; pass < passes; ++pass)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int e = 0; e < 8; ++e) {
-                        const int t = 8 * (lane >> 4) + e - (lane & 15);
+                        const int t = 32 * pass + 8 * (lane >> 4) + e - (lane & 15);
                         if (t < 0 || t >= kn) continue;
+                        const size_t base = ((((size_t)set * km + s) * passes + pass) * 2) * 512;
                         const float v = std::ldexp(w[set * kk + s * kn + t], ew);
                         const uint16_t hb = f32_to_f16_bits(v);
-                        const uint16_t lb = f32_to_f16_bits(v - f16_bits_to_f32(hb));
-                        const size_t base = ((size_t)set * km + s) * 2 * 64 * 8;
-                        img[base + (size_t)lane * 8 + e] = hb;
-                        img[base + 64 * 8 + (size_t)lane * 8 + e] = lb;
+                        halfs[base + (size_t)lane * 8 + e] = hb;
+                        halfs[base + 512 + (size_t)lane * 8 + e] = f32_to_f16_bits(v - f16_bits_to_f32(hb));
                     }
-        }
-        CS_HIP(ctx, hipMemcpyAsync(ctx->d_wfrag, img.data(), kImage, hipMemcpyHostToDevice, stream));
+    }
+}
+
+// Build (or reuse) the fragment image of the float32 weights currently in ctx->d_w[0] (layout in cs_launch.h MfmaWeights), and the
+// rim tables of the two mask weight sets behind the same key.
+int ensure_wfrag(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWeights* E)
+{
+    int nsets = 0;
+    int rc = cached_weight_sets(ctx, km, kn, &nsets);
+    if (rc != CS_OK) return rc;
+    if (km > 17 || kn > 17) return fail(ctx, CS_ERR_INVALID, "the matrix-core weight image holds templates of up to 17 x 17");
+    const std::vector<unsigned char>& key = ctx->w_cached[0];
+    const int kk = km * kn;
+    constexpr size_t kImage = 3 * 17 * 2 * 1024;
+    WeightImage& img = ctx->wfrag;
+    rc = ensure_image(ctx, img, kImage);
+    if (rc != CS_OK) return rc;
+    if (!img.matches(km, kn, key)) {
+        const float* w = reinterpret_cast<const float*>(key.data());
+        std::vector<uint16_t> halfs(kImage / 2, 0);
+        pack_weight_sets(img, w, nsets, km, kn, 1, halfs.data());
+        CS_HIP(ctx, hipMemcpyAsync(img.d, halfs.data(), kImage, hipMemcpyHostToDevice, stream));
         ++ctx->uploads;
         // rim tables of the two mask weight sets (cs_launch.h MfmaWeights::rim), square templates only
         std::vector<float> rim(cs::kRimFloats, 0.0f);
@@ -259,13 +304,11 @@ int ensure_wfrag(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWeight
         CS_HIP(ctx, hipMemcpyAsync(ctx->d_rim, rim.data(), sizeof(float) * cs::kRimFloats, hipMemcpyHostToDevice, stream));
         ++ctx->uploads;
         CS_HIP(ctx, hipStreamSynchronize(stream));    // pageable sources die here
-        ctx->wfrag_key = key;
-        ctx->wfrag_km = km;
-        ctx->wfrag_kn = kn;
+        img.commit(km, kn, key);
     }
-    E->frag = reinterpret_cast<const uint4*>(ctx->d_wfrag);
+    E->frag = reinterpret_cast<const uint4*>(img.d);
     E->rim = reinterpret_cast<const float*>(ctx->d_rim);
-    for (int set = 0; set < 3; ++set) E->unscale[set] = ctx->wfrag_unscale[set];
+    for (int set = 0; set < 3; ++set) E->unscale[set] = img.unscale[set];
     return CS_OK;
 }
 
@@ -274,63 +317,33 @@ int ensure_wfrag(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWeight
 // float32 weights the device holds, rounded once).
 int ensure_wfrag_wide(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaWideWeights* E)
 {
+    int nsets = 0;
+    int rc = cached_weight_sets(ctx, km, kn, &nsets);
+    if (rc != CS_OK) return rc;
+    if (!cs::corr_mfma_wide_fits(km, kn)) return fail(ctx, CS_ERR_INVALID, "the two-pass matrix-core kernel holds templates of up to 33 x 33");
     const std::vector<unsigned char>& key = ctx->w_cached[0];
     const int kk = km * kn;
-    const size_t n_floats = key.size() / 4;
-    if (kk <= 0 || n_floats < (size_t)kk) return fail(ctx, CS_ERR_INVALID, "weights missing for the matrix-core kernel");
-    if (!cs::corr_mfma_wide_fits(km, kn)) return fail(ctx, CS_ERR_INVALID, "the two-pass matrix-core kernel holds templates of up to 33 x 33");
-    const int nsets = (int)std::min<size_t>(3, n_floats / kk);
-    const size_t frag_halfs = (size_t)3 * km * 2 * 2 * 512;
-    const size_t sums_off = frag_halfs * 2;                    // bytes (a multiple of 16)
+    const size_t sums_off = (size_t)3 * km * 2 * 2 * 512 * 2;      // bytes (a multiple of 16)
     const size_t bytes = sums_off + 4 * 33 * sizeof(float);
-    if (bytes > ctx->d_wfrag_wide_bytes) {
-        if (ctx->d_wfrag_wide) {
-            CS_HIP(ctx, hipDeviceSynchronize());   // a queued kernel may still read the old image
-            CS_HIP(ctx, hipFree(ctx->d_wfrag_wide));
-        }
-        ctx->d_wfrag_wide = nullptr;
-        ctx->d_wfrag_wide_bytes = 0;
-        ctx->wfrag_wide_key.clear();
-        CS_HIP(ctx, hipMalloc(&ctx->d_wfrag_wide, bytes));
-        ctx->d_wfrag_wide_bytes = bytes;
-    }
-    if (!(ctx->wfrag_wide_km == km && ctx->wfrag_wide_kn == kn && ctx->wfrag_wide_key == key)) {
+    WeightImage& img = ctx->wfrag_wide;
+    rc = ensure_image(ctx, img, bytes);
+    if (rc != CS_OK) return rc;
+    if (!img.matches(km, kn, key)) {
         const float* w = reinterpret_cast<const float*>(key.data());
-        std::vector<unsigned char> img(bytes, 0);
-        uint16_t* halfs = reinterpret_cast<uint16_t*>(img.data());
-        float* sums = reinterpret_cast<float*>(img.data() + sums_off);
-        for (int set = 0; set < nsets; ++set) {
-            float amax = 0.0f;
-            for (int t = 0; t < kk; ++t) amax = std::max(amax, std::fabs(w[set * kk + t]));
-            int ew = 0;
-            if (amax > 0.0f && std::isfinite(amax)) {
-                int e2;
-                (void)std::frexp(amax, &e2);          // amax = f * 2^e2, f in [0.5, 1)
-                ew = 7 - e2;                           // amax * 2^ew in [64, 128)
-            }
-            ew = std::max(-100, std::min(100, ew));
-            ctx->wfrag_wide_unscale[set] = std::ldexp(1.0f, -ew);
-            for (int s = 0; s < km; ++s)
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int k = 8 * (lane >> 4) + e;
-                            const size_t base = ((((size_t)set * km + s) * 2 + pass) * 2) * 512;
-                            const int t = 32 * pass + k - (lane & 15);
-                            if (t >= 0 && t < kn) {
-                                const float v = std::ldexp(w[set * kk + s * kn + t], ew);
-                                const uint16_t hb = f32_to_f16_bits(v);
-                                const uint16_t lb = f32_to_f16_bits(v - f16_bits_to_f32(hb));
-                                halfs[base + (size_t)lane * 8 + e] = hb;
-                                halfs[base + 512 + (size_t)lane * 8 + e] = lb;
-                            }
-                            // the second pass of the template itself (set 0): k = 16 .. 31 meet no weight (t >= 33), and the kernel
-                            // sends the signal's TAILS of the columns of k - 16 through them: a second copy of the heads
-                            const int t2 = 32 + (k - 16) - (lane & 15);
-                            if (set == 0 && pass == 1 && k >= 16 && t2 >= 0 && t2 < kn)
-                                halfs[base + (size_t)lane * 8 + e] = f32_to_f16_bits(std::ldexp(w[s * kn + t2], ew));
-                        }
-        }
+        std::vector<unsigned char> host(bytes, 0);
+        uint16_t* halfs = reinterpret_cast<uint16_t*>(host.data());
+        float* sums = reinterpret_cast<float*>(host.data() + sums_off);
+        pack_weight_sets(img, w, nsets, km, kn, 2, halfs);
+        // the second pass of the template itself (set 0): k = 16 .. 31 meet no weight (t >= 33), and the kernel sends the signal's
+        // TAILS of the columns of k - 16 through them: a second copy of the heads
+        const int ew0 = weight_scale_exponent(w, kk);
+        for (int s = 0; s < km; ++s)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int e = 0; e < 8; ++e) {
+                    const int k = 8 * (lane >> 4) + e, t2 = 32 + (k - 16) - (lane & 15);
+                    if (k >= 16 && t2 >= 0 && t2 < kn)
+                        halfs[(((size_t)s * 2 + 1) * 2) * 512 + (size_t)lane * 8 + e] = f32_to_f16_bits(std::ldexp(w[s * kn + t2], ew0));
+                }
         if (nsets == 3)
             for (int set = 0; set < 2; ++set) {
                 const float* ws = w + (1 + set) * kk;
@@ -345,16 +358,14 @@ int ensure_wfrag_wide(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaW
                     sums[(2 + set) * 33 + t] = (float)acc;
                 }
             }
-        CS_HIP(ctx, hipMemcpyAsync(ctx->d_wfrag_wide, img.data(), bytes, hipMemcpyHostToDevice, stream));
+        CS_HIP(ctx, hipMemcpyAsync(img.d, host.data(), bytes, hipMemcpyHostToDevice, stream));
         ++ctx->uploads;
         CS_HIP(ctx, hipStreamSynchronize(stream));    // the pageable source dies here
-        ctx->wfrag_wide_key = key;
-        ctx->wfrag_wide_km = km;
-        ctx->wfrag_wide_kn = kn;
+        img.commit(km, kn, key);
     }
-    E->frag = reinterpret_cast<const uint4*>(ctx->d_wfrag_wide);
-    E->sums = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ctx->d_wfrag_wide) + sums_off);
-    for (int set = 0; set < 3; ++set) E->unscale[set] = ctx->wfrag_wide_unscale[set];
+    E->frag = reinterpret_cast<const uint4*>(img.d);
+    E->sums = reinterpret_cast<const float*>(reinterpret_cast<const char*>(img.d) + sums_off);
+    for (int set = 0; set < 3; ++set) E->unscale[set] = img.unscale[set];
     E->plane_only = std::getenv("CHROMOSIGHT_HIP_WIDE_PLANE") ? 1 : 0;
     E->plane_only_staging = std::getenv("CHROMOSIGHT_HIP_WIDE_SLOW") ? 1 : 0;
     E->one_launch = std::getenv("CHROMOSIGHT_HIP_WIDE_ONE_LAUNCH") ? 1 : std::getenv("CHROMOSIGHT_HIP_WIDE_TWO_LAUNCHES") ? 2 : 0;
@@ -366,67 +377,29 @@ int ensure_wfrag_wide(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaW
 // x km rows x NP passes x {head, tail} x 1 KiB (1.5 MB at 81 x 81: L2-resident).
 int ensure_wfrag_large(cs_ctx* ctx, hipStream_t stream, int km, int kn, cs::MfmaLargeWeights* E)
 {
-    const std::vector<unsigned char>& key = ctx->w_cached[0];
-    const int kk = km * kn;
-    const size_t n_floats = key.size() / 4;
-    if (kk <= 0 || n_floats < (size_t)kk) return fail(ctx, CS_ERR_INVALID, "weights missing for the matrix-core kernel");
+    int nsets = 0;
+    int rc = cached_weight_sets(ctx, km, kn, &nsets);
+    if (rc != CS_OK) return rc;
     if (!cs::corr_mfma_large_fits(km, kn)) return fail(ctx, CS_ERR_INVALID, "the large-template matrix-core kernel holds templates of 34 .. 81");
+    const std::vector<unsigned char>& key = ctx->w_cached[0];
     const int np = cs::corr_mfma_large_passes(kn);
-    const int nsets = (int)std::min<size_t>(3, n_floats / kk);
     const size_t bytes = (size_t)3 * km * np * 2 * 512 * 2;
-    if (bytes > ctx->d_wfrag_large_bytes) {
-        if (ctx->d_wfrag_large) {
-            CS_HIP(ctx, hipDeviceSynchronize());   // a queued kernel may still read the old image
-            CS_HIP(ctx, hipFree(ctx->d_wfrag_large));
-        }
-        ctx->d_wfrag_large = nullptr;
-        ctx->d_wfrag_large_bytes = 0;
-        ctx->wfrag_large_key.clear();
-        CS_HIP(ctx, hipMalloc(&ctx->d_wfrag_large, bytes));
-        ctx->d_wfrag_large_bytes = bytes;
-    }
-    if (!(ctx->wfrag_large_km == km && ctx->wfrag_large_kn == kn && ctx->wfrag_large_key == key)) {
-        const float* w = reinterpret_cast<const float*>(key.data());
-        std::vector<unsigned char> img(bytes, 0);
-        uint16_t* halfs = reinterpret_cast<uint16_t*>(img.data());
-        for (int set = 0; set < nsets; ++set) {
-            float amax = 0.0f;
-            for (int t = 0; t < kk; ++t) amax = std::max(amax, std::fabs(w[set * kk + t]));
-            int ew = 0;
-            if (amax > 0.0f && std::isfinite(amax)) {
-                int e2;
-                (void)std::frexp(amax, &e2);          // amax = f * 2^e2, f in [0.5, 1)
-                ew = 7 - e2;                           // amax * 2^ew in [64, 128)
-            }
-            ew = std::max(-100, std::min(100, ew));
-            ctx->wfrag_large_unscale[set] = std::ldexp(1.0f, -ew);
-            for (int s = 0; s < km; ++s)
-                for (int pass = 0; pass < np; ++pass)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 8; ++e) {
-                            const int t = 32 * pass + 8 * (lane >> 4) + e - (lane & 15);
-                            if (t < 0 || t >= kn) continue;
-                            const size_t base = ((((size_t)set * km + s) * np + pass) * 2) * 512;
-                            const float v = std::ldexp(w[set * kk + s * kn + t], ew);
-                            const uint16_t hb = f32_to_f16_bits(v);
-                            halfs[base + (size_t)lane * 8 + e] = hb;
-                            halfs[base + 512 + (size_t)lane * 8 + e] = f32_to_f16_bits(v - f16_bits_to_f32(hb));
-                        }
-        }
-        CS_HIP(ctx, hipMemcpyAsync(ctx->d_wfrag_large, img.data(), bytes, hipMemcpyHostToDevice, stream));
+    WeightImage& img = ctx->wfrag_large;
+    rc = ensure_image(ctx, img, bytes);
+    if (rc != CS_OK) return rc;
+    if (!img.matches(km, kn, key)) {
+        std::vector<unsigned char> host(bytes, 0);
+        pack_weight_sets(img, reinterpret_cast<const float*>(key.data()), nsets, km, kn, np, reinterpret_cast<uint16_t*>(host.data()));
+        CS_HIP(ctx, hipMemcpyAsync(img.d, host.data(), bytes, hipMemcpyHostToDevice, stream));
         ++ctx->uploads;
         CS_HIP(ctx, hipStreamSynchronize(stream));    // the pageable source dies here
-        ctx->wfrag_large_key = key;
-        ctx->wfrag_large_km = km;
-        ctx->wfrag_large_kn = kn;
+        img.commit(km, kn, key);
     }
-    E->frag = reinterpret_cast<const uint4*>(ctx->d_wfrag_large);
-    for (int set = 0; set < 3; ++set) E->unscale[set] = ctx->wfrag_large_unscale[set];
+    E->frag = reinterpret_cast<const uint4*>(img.d);
+    for (int set = 0; set < 3; ++set) E->unscale[set] = img.unscale[set];
     E->passes = np;
     return CS_OK;
 }
-
-bool fast_available(int km, int kn, int* K);
 
 // Rank-revealing factorisation of a km x kn float64 matrix by elimination with complete pivoting: M = sum_i u_i v_i^T with
 // u_i = R[:, q] / R[p, q] (|u_i| <= 1) and v_i = R[p, :], R the residual and (p, q) its largest entry.  Returns the rank, or -1 when
@@ -484,6 +457,37 @@ void append_lowrank_table(std::vector<double>& w, int km, int kn, const std::vec
     w.insert(w.end(), UB.begin(), UB.begin() + (size_t)rb * km);
 }
 
+// One pass over the environment instead of one per switch (std::getenv walks it each time; a correlation call reads the switches
+// twice, in build_args and in launch_corr): 0.18 us against 1.0 us for sixteen getenv calls in a process with 85 variables.
+DispatchSwitches read_dispatch_switches()
+{
+    DispatchSwitches sw = {};
+    sw.mfma = sw.mfma_reg = sw.large = sw.lowrank = -1;
+    const struct { const char* name; bool* flag; int* digit; } known[] = {
+        {"FORCE_GENERIC", &sw.force_generic, nullptr}, {"NO_MFMA", &sw.no_mfma, nullptr}, {"NO_WIDE", &sw.no_wide, nullptr},
+        {"WIDE_ALL", &sw.wide_all, nullptr}, {"NO_LARGE", &sw.no_large, nullptr}, {"NO_SEPARABLE", &sw.no_separable, nullptr},
+        {"SEPARABLE_FIRST", &sw.separable_first, nullptr}, {"NO_REGULAR_MASK", &sw.no_regular_mask, nullptr},
+        {"FULL_MASK_TABLES", &sw.full_mask_tables, nullptr}, {"MFMA_NORSYM", &sw.mfma_norsym, nullptr},
+        {"NO_SYMMETRY", &sw.no_symmetry, nullptr}, {"DEBUG", &sw.debug, nullptr}, {"MFMA", nullptr, &sw.mfma},
+        {"MFMA_REG", nullptr, &sw.mfma_reg}, {"LARGE", nullptr, &sw.large}, {"LOWRANK", nullptr, &sw.lowrank},
+    };
+    constexpr size_t kPrefix = sizeof("CHROMOSIGHT_HIP_") - 1;
+    for (char** e = environ; e && *e; ++e) {
+        if ((*e)[0] != 'C' || std::strncmp(*e, "CHROMOSIGHT_HIP_", kPrefix) != 0) continue;
+        const char* name = *e + kPrefix;
+        const char* eq = std::strchr(name, '=');
+        if (!eq) continue;
+        for (const auto& k : known)
+            if (std::strlen(k.name) == (size_t)(eq - name) && std::strncmp(k.name, name, eq - name) == 0) {
+                if (k.flag) *k.flag = true;
+                else *k.digit = eq[1] == '1' ? 1 : eq[1] == '0' ? 0 : -1;
+            }
+    }
+    return sw;
+}
+
+// ---- kernel selection: the predicates of the routes of launch_corr (the route lists below state their order) ----------------------
+
 // Which float32 calls take the separable kernel of truncated-SVD templates (cs_corr_lowrank.hip): templates whose factors
 // build_args cached (--tsvd) -- and plain cross-correlations, which carry no tsvd marker, only under the forced setting.
 // CHROMOSIGHT_HIP_LOWRANK=1: every such call the kernel supports; =0: none (the kernels of the full template).  Unset: where it
@@ -491,12 +495,10 @@ void append_lowrank_table(std::vector<double>& w, int km, int kn, const std::vec
 // 34 .. 81, which the runtime-size kernel serves otherwise: dense 4096^2 4.0x at 41, 4.8x at 61; C4' band with per-bin masks 1.3x at
 // 41, 1.8x at 61.  Candidate sinks with a side of 34 .. 41: on the C4' band 1.03x the matrix-core kernel of cs_corr_large.hip at 41,
 // 0.63x at 61.  The matrix-core kernels of up to 33 x 33 stay ahead on every shape measured (loops / borders 17, stripes 31, loops 33).
-bool lowrank_wanted(const cs::CorrArgs<float>& A)
+static bool lowrank_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
 {
     if (A.w_lr <= 0 || !cs::corr_lowrank_supports(A)) return false;
-    const char* e = std::getenv("CHROMOSIGHT_HIP_LOWRANK");
-    if (e && e[0] == '0') return false;
-    if (e && e[0] == '1') return true;
+    if (sw.lowrank >= 0) return sw.lowrank == 1;
     const int side = std::max(A.km, A.kn);
     if (side < 34 || (A.w_lr + A.w_lr2 + 2) * (A.km + A.kn) * 2 > A.km * A.kn) return false;
     return A.out.ptr ? true : side <= 41;
@@ -506,31 +508,71 @@ bool lowrank_wanted(const cs::CorrArgs<float>& A)
 // `--win-size` makes (cli/chromosight.py:365-370) and the 19 x 19 .. 33 x 33 templates of API users -- in every container
 // the runtime-size kernel served (bands and dense maps, float32 and float64, any mask, n_obs, plain cross-correlations).
 // CHROMOSIGHT_HIP_NO_MFMA=1 / CHROMOSIGHT_HIP_NO_WIDE=1: never (the runtime-size kernel: the in-library cross-check).
-bool mfma_wide_wanted(const cs::CorrArgs<float>& A)
+static bool mfma_wide_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
 {
     // (templates of up to 17 x 17 have their own instances; CHROMOSIGHT_HIP_WIDE_ALL=1 sends them here too: a measurement switch)
-    if (!cs::corr_mfma_wide_fits(A.km, A.kn) || (A.km <= 17 && A.kn <= 17 && !std::getenv("CHROMOSIGHT_HIP_WIDE_ALL"))) return false;
+    if (!cs::corr_mfma_wide_fits(A.km, A.kn) || (A.km <= 17 && A.kn <= 17 && !sw.wide_all)) return false;
     if (A.sig.counts || A.sig.layout == CS_LAYOUT_BAND_LAZY) return false;
     if (!A.out.ptr && !(A.cand_keys && A.cand_count && !A.defer_args && A.ks.cand_cmin > 0.0f)) return false;     // a map, or a candidate sink
-    if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA") || std::getenv("CHROMOSIGHT_HIP_NO_WIDE")) return false;
-    return true;
+    return !sw.no_mfma && !sw.no_wide;
 }
 
 // Which float32 calls take the matrix-core kernel of the templates with a side of 34 .. 81 (cs_corr_large.hip): candidate
 // sinks without a map (cs_candidates, cs_candidates_tiles, the detect flow: the 81 x 81 `centromeres` template) in every
 // container the runtime-size kernel served.  Map calls stay on the runtime-size kernel unless CHROMOSIGHT_HIP_LARGE=1;
 // CHROMOSIGHT_HIP_NO_LARGE=1 / CHROMOSIGHT_HIP_NO_MFMA=1: never (the runtime-size kernel: the in-library cross-check).
-bool mfma_large_wanted(const cs::CorrArgs<float>& A)
+static bool mfma_large_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
 {
     if (!cs::corr_mfma_large_fits(A.km, A.kn)) return false;
     if (A.sig.counts || A.sig.layout == CS_LAYOUT_BAND_LAZY || A.defer_args) return false;
-    if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA") || std::getenv("CHROMOSIGHT_HIP_NO_LARGE")) return false;
+    if (sw.no_mfma || sw.no_large) return false;
     if (!A.out.ptr) return A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f;          // a candidate sink
-    const char* e = std::getenv("CHROMOSIGHT_HIP_LARGE");
-    return e && e[0] == '1';
+    return sw.large == 1;
 }
 
-// Which float32 calls go to the matrix cores (cs_corr_mfma.hip).  Default: unmasked dense float32 maps
+// Which float32 calls take the masked matrix-core tile kernel (cs_corr_mfma.hip, the factorised mask tables + the persistent tile
+// kernel): per-bin masks in full mode (the detect / quantify configuration), odd square templates of up to 17 x 17.
+static bool mfma_reg_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
+{
+    if (A.mask_mode != CS_MASK_BINS || !A.full || A.km != A.kn || A.km > 17 || A.km < 3 || !(A.km & 1)) return false;
+    if (sw.wide_all) return false;
+    if (A.xcorr_only) return false;            // (float64 containers are narrowed row by row first, see narrow_f64_rows)
+    if ((A.sig.layout == CS_LAYOUT_BAND ? A.sig.band_w : A.ns) < 4) return false;      // 16-byte staging pieces
+    // (candidate mode without a sink -- the map fallback of find_candidates -- runs on the kernels that decide the screen
+    // at run time: the tile kernel's candidate instance has no map output)
+    if (A.ks.cand_cmin > 0.0f && !A.cand_keys) return false;
+    if (sw.no_mfma) return false;
+    // default: templates of 15 x 15 and 17 x 17 -- measured on the 234- and 1001-diagonal bands (tools/time_templates.py,
+    // profiles/*_template_kernels.txt): 17 x 17 mirrored rows 2.01 vs 2.56 ms, 17 x 17 general 2.27 vs 3.01, 15 x 15 2.24 vs
+    // 2.72; at 13 x 13 it wins only on the wide band (2.29 vs 2.51, 0.251 vs 0.235 on the narrow one), below that the
+    // streaming kernel does (the tile kernel always walks 17 template rows).  CHROMOSIGHT_HIP_MFMA_REG=1 sends every
+    // compatible call here, =0 none
+    if (sw.mfma_reg >= 0) return sw.mfma_reg == 1;
+    if (sw.mfma == 1) return false;      // the general matrix-core kernel was asked for by name
+    return A.km >= 15;
+}
+
+// the fully unrolled streaming kernels (cs_corr_fast.hip, one object per size): float32 and float64 launcher of a template size
+struct FastKernel {
+    int K;
+    void (*tile)(int ms, int ns, int band_w, int n_cu, int* tw, int* th);
+    int (*f32)(const cs::CorrArgs<float>&, hipStream_t);
+    int (*f64)(const cs::CorrArgs<double>&, hipStream_t);
+};
+static const FastKernel* fast_kernel(int km, int kn)
+{
+#ifdef CS_HAVE_FAST
+#define CS_FAST(K) {K, cs::corr_fast_tile_k##K, cs::launch_corr_fast_f32_k##K, cs::launch_corr_fast_f64_k##K}
+    static const FastKernel table[] = {CS_FAST(7), CS_FAST(9), CS_FAST(11), CS_FAST(13), CS_FAST(15), CS_FAST(17)};
+#undef CS_FAST
+    if (km == kn)
+        for (const FastKernel& f : table)
+            if (f.K == km) return &f;
+#endif
+    return nullptr;
+}
+
+// Which float32 calls take the other instances of cs_corr_mfma.hip.  Default: unmasked dense float32 maps
 // (cs_normxcorr2 without a mask: the API / benchmark configuration) whenever the template is large
 // (>= 13 x 13 entries: every template costs a full 17-row pass there, so small ones are cheaper on the
 // packed-FMA kernel -- measured 4096^2: 17x17 0.115 vs 0.185 ms (no symmetry), 13x13 0.124 vs 0.127,
@@ -538,57 +580,46 @@ bool mfma_large_wanted(const cs::CorrArgs<float>& A)
 // 2048^2 11x11 0.035 vs 0.042 ms, 1024^2 9x9 0.014 vs 0.019) or the template has no streaming kernel
 // (rectangular sizes).  CHROMOSIGHT_HIP_MFMA=1: every call with a template of up to 17 x 17
 // (masked / banded maps run the general, slower, matrix-core kernel -- a test switch);
-// CHROMOSIGHT_HIP_NO_MFMA=1: never.  Read per call so that tests can flip them.
-// per-bin masks (detect / quantify configuration): opt-in for now (CHROMOSIGHT_HIP_MFMA_REG=1)
-bool mfma_reg_wanted(const cs::CorrArgs<float>& A)
-{
-    if (A.mask_mode != CS_MASK_BINS || !A.full || A.km != A.kn || A.km > 17 || A.km < 3 || !(A.km & 1)) return false;
-    if (std::getenv("CHROMOSIGHT_HIP_WIDE_ALL")) return false;
-    if (A.xcorr_only) return false;            // (float64 containers are narrowed row by row first, see launch_corr)
-    if ((A.sig.layout == CS_LAYOUT_BAND ? A.sig.band_w : A.ns) < 4) return false;      // 16-byte staging pieces
-    if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA")) return false;
-    // default: templates of 15 x 15 and 17 x 17 -- measured on the 234- and 1001-diagonal bands (tools/time_templates.py,
-    // profiles/*_template_kernels.txt): 17 x 17 mirrored rows 2.01 vs 2.56 ms, 17 x 17 general 2.27 vs 3.01, 15 x 15 2.24 vs
-    // 2.72; at 13 x 13 it wins only on the wide band (2.29 vs 2.51, 0.251 vs 0.235 on the narrow one), below that the
-    // streaming kernel does (the tile kernel always walks 17 template rows).  CHROMOSIGHT_HIP_MFMA_REG=1 sends every
-    // compatible call here, =0 none
-    const char* e = std::getenv("CHROMOSIGHT_HIP_MFMA_REG");
-    if (e && e[0] == '1') return true;
-    if (e && e[0] == '0') return false;
-    const char* general = std::getenv("CHROMOSIGHT_HIP_MFMA");
-    if (general && general[0] == '1') return false;      // the general matrix-core kernel was asked for by name
-    return A.km >= 15;
-}
-
-bool mfma_wanted(const cs::CorrArgs<float>& A)
+// CHROMOSIGHT_HIP_NO_MFMA=1: never.
+static bool mfma_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
 {
     if (A.km < 1 || A.kn < 1 || A.km > 17 || A.kn > 17) return false;
-    if (std::getenv("CHROMOSIGHT_HIP_NO_MFMA") || std::getenv("CHROMOSIGHT_HIP_WIDE_ALL")) return false;
-    const char* e = std::getenv("CHROMOSIGHT_HIP_MFMA");
-    if (e && e[0] == '1') return true;
+    if (sw.no_mfma || sw.wide_all) return false;
+    if (sw.mfma == 1) return true;
     const bool dense_f32 = A.mask_mode == 0 && A.sig.layout == 0 && A.out.layout == 0 && !A.nobs.ptr;
-    int K = 0;
     const long long px = (long long)(A.row_end - A.row_begin) * A.ns;
-    return dense_f32 && (A.km * A.kn >= 169 || px <= 6000000 || !fast_available(A.km, A.kn, &K));
+    return dense_f32 && (A.km * A.kn >= 169 || px <= 6000000 || !fast_kernel(A.km, A.kn));
 }
 
-bool fast_available(int km, int kn, int* K)
+// the streaming kernels write n_obs next to the coefficient (same index), so both maps must share
+// one geometry; plain cross-correlations run their unmasked instance
+template <typename TC>
+static bool stream_wanted(const cs::CorrArgs<TC>& A, const DispatchSwitches& sw)
 {
-    (void)km;
-    (void)kn;
-    (void)K;
-#ifdef CS_HAVE_FAST
-    if (km != kn) return false;
-    switch (km) {
-        case 7: case 9: case 11: case 13: case 15: case 17:
-            *K = km;
-            return true;
-        default:
-            return false;
-    }
-#else
-    return false;
-#endif
+    if (A.nobs.ptr && (A.nobs.layout != A.out.layout || A.nobs.ld != A.out.ld || A.nobs.band_lo != A.out.band_lo ||
+                       A.nobs.band_w != A.out.band_w || A.nobs.row0 != A.out.row0))
+        return false;
+    if (A.xcorr_only && (A.mask_mode != 0 || A.full || A.sym_upper)) return false;
+    if (sizeof(TC) == 4 && sw.wide_all) return false;       // (float32: on to the two-pass kernel)
+    return fast_kernel(A.km, A.kn) != nullptr;
+}
+
+// Which float32 calls take the separable sums of cs_corr_sep.hip: templates that are an outer product (the 31 x 31 stripes).
+// (An outer product that also fits the two-pass matrix-core kernel: that one on wide bands -- measured on the 31 x 31 stripes,
+// profiles/r06_template_kernels.txt: 1001 diagonals 5.40 vs 6.92 ms, 234 diagonals 0.577 vs 0.517)
+static bool separable_wanted(const cs::CorrArgs<float>& A, const DispatchSwitches& sw)
+{
+    if (!A.w_rank1 || A.xcorr_only || sw.no_separable || !cs::corr_sep_fits(A.km, A.kn, A.mask_mode != 0)) return false;
+    return !(mfma_wide_wanted(A, sw) && A.out.layout == CS_LAYOUT_BAND && A.out.band_w >= 512 && !sw.separable_first);
+}
+
+// the diagonals of the output (CorrArgs::out_lo / out_hi)
+template <typename TC>
+void out_diagonals(cs::CorrArgs<TC>& A)
+{
+    const bool band = A.out.layout == CS_LAYOUT_BAND;
+    A.out_lo = band ? A.out.band_lo : -(1 << 30);
+    A.out_hi = band ? A.out.band_lo + A.out.band_w - 1 : (1 << 30);
 }
 
 // aligned_x: the generic kernel starts the x tiles of a row block at a multiple of the tile width,
@@ -599,16 +630,13 @@ void fill_grid(cs::CorrArgs<TC>& A, int tw, int th, bool aligned_x = true)
     A.tile_w = tw;
     A.tile_h = th;
     A.tiles_y = (A.row_end - A.row_begin + th - 1) / th;
+    out_diagonals(A);
     if (A.out.layout == CS_LAYOUT_BAND) {
-        A.out_lo = A.out.band_lo;
-        A.out_hi = A.out.band_lo + A.out.band_w - 1;
         const long long span = (long long)(A.out_hi - A.out_lo) + th + tw - 1;
         A.tiles_x = aligned_x ? (int)(span / tw) + 2 : (int)(span / tw);
         const int max_x = (A.ns + tw - 1) / tw;
         if (A.tiles_x > max_x) A.tiles_x = max_x;
     } else {
-        A.out_lo = -(1 << 30);
-        A.out_hi = (1 << 30);
         A.tiles_x = (A.ns + tw - 1) / tw;
     }
 }
@@ -616,15 +644,16 @@ void fill_grid(cs::CorrArgs<TC>& A, int tw, int th, bool aligned_x = true)
 // Decide whether the factorised per-bin mask path applies and, if so, build its tables in the
 // context's scratch buffer (cs_mask_prep.hip).  K = template size served by a streaming kernel.
 template <typename TC>
-int prepare_regular_mask(cs_ctx* ctx, cs::CorrArgs<TC>& A, int K, hipStream_t stream, bool rim_in_kernel = false, bool tile_reader = false)
+int prepare_regular_mask(cs_ctx* ctx, cs::CorrArgs<TC>& A, const DispatchSwitches& sw, int K, hipStream_t stream, bool rim_in_kernel = false,
+                         bool tile_reader = false)
 {
     A.reg_mode = 0;
     A.fix_on = 0;
     A.rim_in_kernel = 0;
-    if (std::getenv("CHROMOSIGHT_HIP_DEBUG"))
+    if (sw.debug)
         fprintf(stderr, "[chromosight_hip] mask_mode=%d full=%d sym_upper=%d ms=%d ns=%d out_layout=%d out_lo=%d out_hi=%d max_dist=%d\n",
                 A.mask_mode, A.full, A.sym_upper, A.ms, A.ns, A.out.layout, A.out_lo, A.out_hi, A.max_dist);
-    if (A.mask_mode != CS_MASK_BINS || !A.full || std::getenv("CHROMOSIGHT_HIP_NO_REGULAR_MASK")) return CS_OK;
+    if (A.mask_mode != CS_MASK_BINS || !A.full || sw.no_regular_mask) return CS_OK;
     if (A.ms < 2 * K || A.ns < 2 * K) return CS_OK;
     const int KH = (K - 1) / 2;
     const bool band_out = A.out.layout == CS_LAYOUT_BAND;
@@ -705,7 +734,7 @@ int prepare_regular_mask(cs_ctx* ctx, cs::CorrArgs<TC>& A, int K, hipStream_t st
     P.side = side;
     P.fix_rows = fix_rows;
     P.fix_cols = fix_cols;
-    if (tile_reader && edge_tables && !edge_records && (A.row_begin > 0 || A.row_end < A.ms) && !std::getenv("CHROMOSIGHT_HIP_FULL_MASK_TABLES")) {
+    if (tile_reader && edge_tables && !edge_records && (A.row_begin > 0 || A.row_end < A.ms) && !sw.full_mask_tables) {
         // A row window read by the 64 x 64 tiles of the matrix-core kernel (a rank's share of a row-split block): the table entries
         // of its rows and of the columns its strip of tiles reaches (J0 + lane, J0 <= I0 + out_lo + 64 (tiles_x - 1)), and the frame
         // rows only when the window touches them -- the tables of all 200 000 bins cost 19 us in front of an eighth's 220 us of tiles
@@ -750,224 +779,203 @@ int prepare_regular_mask(cs_ctx* ctx, cs::CorrArgs<TC>& A, int K, hipStream_t st
     return CS_OK;
 }
 
-template <typename TC>
-int launch_corr(cs_ctx* ctx, cs::CorrArgs<TC>& A, hipStream_t stream, bool allow_fast);
+// ---- kernel selection: the routes ---------------------------------------------------------------------------------------------
+// A route is a predicate (*_wanted above: pure, of the argument block and the switches) and a run (prepare + launch) that returns the
+// call's result: CS_OK with ctx->last_kernel (and ctx->cand_fused) set, CS_NEED_MAP, or an error.  Two runs may also answer
+// kNextRoute: the route does not take the call after all, nothing was launched.  launch_corr below states the order.
+constexpr int kNextRoute = CS_NEED_MAP + 1;
 
-// internal status of launch_corr<float>: a candidate sink was given without a map, and the kernel that would serve the
-// call writes maps (nothing was launched that matters: the caller allocates the map and calls again)
-
-// the streaming kernels write n_obs next to the coefficient (same index), so both maps must share
-// one geometry; plain cross-correlations run their unmasked instance
-template <typename TC>
-bool fast_compatible(const cs::CorrArgs<TC>& A)
+// what a launcher returned (cs_launch.h LaunchStatus), as the result of a call that gave a map ...
+static int map_result(cs_ctx* ctx, int km, int kn, int rc)
 {
-    if (A.nobs.ptr && (A.nobs.layout != A.out.layout || A.nobs.ld != A.out.ld || A.nobs.band_lo != A.out.band_lo ||
-                       A.nobs.band_w != A.out.band_w || A.nobs.row0 != A.out.row0))
-        return false;
-    if (A.xcorr_only && (A.mask_mode != 0 || A.full || A.sym_upper)) return false;
-    return true;
+    if (rc == cs::kLaunchNoFit) return fail(ctx, CS_ERR_UNSUPPORTED, "template %dx%d does not fit the kernel that serves it (160 KiB of LDS, 2^31 tiles)", km, kn);
+    if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return CS_OK;
 }
 
-template <>
-int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, bool allow_fast)
+// ... and of one that may have given a candidate sink instead
+static int sink_result(cs_ctx* ctx, int rc)
 {
-    int K = 0, tw, th, rc;
+    if (rc == cs::kLaunchNeedMap) return CS_NEED_MAP;
+    if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return CS_OK;
+}
+
+// A float64 container (the pipeline keeps the detrended band in float64 for the exact re-scoring of the candidates) in front of a
+// tile kernel, float32 arithmetic: the rows the windows reach are rounded into context scratch, `width` values each -- what the
+// streaming kernel does pixel by pixel -- 12 B of traffic per pixel for a kernel 1.3x faster
+static int narrow_f64_rows(cs_ctx* ctx, cs::CorrArgs<float>& A, int width, hipStream_t stream)
+{
+    const int kh = (A.km - 1) / 2;
+    const int p_lo = std::max(0, A.row_begin - kh), p_hi = std::min(A.ms, A.row_end + (A.km - 1) - kh);
+    const long long ld = ((long long)width + 15) / 16 * 16;
+    int rc = ensure_scratch(ctx, &ctx->d_narrow, &ctx->d_narrow_bytes, (size_t)(p_hi - p_lo) * (size_t)ld * 4);
+    if (rc != CS_OK) return rc;
+    const double* src = reinterpret_cast<const double*>(A.sig.ptr) + ((long long)p_lo - A.sig.row0) * A.sig.ld;
+    rc = cs::launch_narrow_rows(src, A.sig.ld, reinterpret_cast<float*>(ctx->d_narrow), ld, p_hi - p_lo, width, ctx->n_cu, stream);
+    if (rc != 0) return fail(ctx, CS_ERR_HIP, "narrowing kernel failed: %s", hipGetErrorString((hipError_t)rc));
+    A.sig.ptr = ctx->d_narrow;
+    A.sig.ld = ld;
+    A.sig.row0 = p_lo;
+    A.sig_is_f64 = 0;
+    return CS_OK;
+}
+
+// truncated-SVD templates of low rank: row and column passes.  The launcher refuses a template, layout or call form it does not take
+// before anything is launched
+static int run_lowrank(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    const int rc = cs::launch_corr_lowrank_f32(A, stream);
+    if (rc == cs::kLaunchNoFit || rc == cs::kLaunchNeedMap || rc == cs::kLaunchDeclined) return kNextRoute;
+    if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    ctx->last_kernel = CS_KERNEL_LOWRANK;
+    return CS_OK;
+}
+
+// the tile kernels of cs_corr_mfma.hip: weight image, launch, and which instance ran
+static int launch_tile_kernel(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    cs::MfmaWeights E;
+    int rc = ensure_wfrag(ctx, stream, A.km, A.kn, &E);
+    if (rc != CS_OK) return rc;
+    int path = 0;
+    rc = cs::launch_corr_mfma_f32(A, E, stream, &path);
+    ctx->last_kernel = path == 1 ? CS_KERNEL_MFMA_DENSE : path == 2 ? CS_KERNEL_MFMA_REG : path == 3 ? CS_KERNEL_MFMA_LIST : CS_KERNEL_MFMA;
+    return rc;
+}
+
+// per-bin masks on the matrix cores.  Declines when the factorised mask tables do not apply: A.out_lo / out_hi stay set, and
+// prepare_regular_mask has zeroed reg_mode / fix_on / rim_in_kernel for the routes that follow
+static int run_mfma_reg(cs_ctx* ctx, cs::CorrArgs<float>& A, const DispatchSwitches& sw, hipStream_t stream)
+{
+    out_diagonals(A);
+    if (A.cand_keys) {                   // candidate sink: only the scanned diagonals (the map path trims in the compaction)
+        A.out_lo = std::max(A.out_lo, A.cand_dlo);
+        A.out_hi = std::min(A.out_hi, A.cand_dhi);
+    }
+    // (the mirrored-row instance of the tile kernel forms the corrections of the edge diagonals itself: no records)
+    int rc = prepare_regular_mask<float>(ctx, A, sw, A.km, stream, A.mfma_rsym != 0, true);
+    if (rc != CS_OK) return rc;
+    if (A.reg_mode != 1) return kNextRoute;
+    if (A.sig_is_f64) {
+        rc = narrow_f64_rows(ctx, A, A.sig.layout == CS_LAYOUT_BAND ? A.sig.band_w : A.ns, stream);
+        if (rc != CS_OK) return rc;
+    }
+    rc = sink_result(ctx, launch_tile_kernel(ctx, A, stream));
+    if (rc == CS_OK && (ctx->last_kernel == CS_KERNEL_MFMA_REG || ctx->last_kernel == CS_KERNEL_MFMA_LIST) && A.cand_keys) ctx->cand_fused = true;
+    return rc;
+}
+
+// template side 18 .. 33: maps, and candidate sinks (the kernel appends the candidates itself)
+static int run_mfma_wide(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    cs::MfmaWideWeights E;
+    int rc = ensure_wfrag_wide(ctx, stream, A.km, A.kn, &E);
+    if (rc != CS_OK) return rc;
+    const bool sink = !A.out.ptr;
+    ctx->last_kernel = CS_KERNEL_MFMA_WIDE;
+    rc = cs::launch_corr_mfma_wide_f32(A, E, stream);
+    rc = sink ? sink_result(ctx, rc) : map_result(ctx, A.km, A.kn, rc);
+    if (rc == CS_OK && sink) ctx->cand_fused = true;
+    return rc;
+}
+
+// template side 34 .. 81: candidate sinks (the kernel appends the candidates itself; a tile list is walked as listed) and, under
+// CHROMOSIGHT_HIP_LARGE=1, maps
+static int run_mfma_large(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    cs::MfmaLargeWeights E;
+    int rc = ensure_wfrag_large(ctx, stream, A.km, A.kn, &E);
+    if (rc != CS_OK) return rc;
+    const bool sink = !A.out.ptr;
+    ctx->last_kernel = CS_KERNEL_MFMA_LARGE;
+    rc = sink_result(ctx, cs::launch_corr_mfma_large_f32(A, E, stream));
+    if (rc == CS_OK && sink) ctx->cand_fused = true;
+    return rc;
+}
+
+// the dense and the general instance of the tile kernel
+static int run_mfma(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    if (A.sig_is_f64 && A.mask_mode == 0 && A.sig.layout == 0 && A.out.layout == 0 && !A.nobs.ptr) {
+        const int rc = narrow_f64_rows(ctx, A, A.ns, stream);      // so that the persistent tile kernel can stage them
+        if (rc != CS_OK) return rc;
+    }
+    return map_result(ctx, A.km, A.kn, launch_tile_kernel(ctx, A, stream));
+}
+
+template <typename TC>
+static int run_stream(cs_ctx* ctx, cs::CorrArgs<TC>& A, const DispatchSwitches& sw, hipStream_t stream)
+{
+    const FastKernel* f = fast_kernel(A.km, A.kn);
+    int tw, th;
+    ctx->last_kernel = CS_KERNEL_STREAM;
+    f->tile(A.row_end - A.row_begin, A.ns, A.out.layout == 1 ? A.out.band_w : 0, ctx->n_cu, &tw, &th);
+    fill_grid(A, tw, th, false);
+    int rc = prepare_regular_mask<TC>(ctx, A, sw, f->K, stream);
+    if (rc != CS_OK) return rc;
+    if constexpr (sizeof(TC) == 4) rc = f->f32(A, stream);
+    else rc = f->f64(A, stream);
+    return map_result(ctx, A.km, A.kn, rc);
+}
+
+static int run_separable(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    int tw, th;
+    ctx->last_kernel = CS_KERNEL_SEPARABLE;
+    cs::corr_sep_tile(&tw, &th);
+    fill_grid(A, tw, th);
+    return map_result(ctx, A.km, A.kn, cs::launch_corr_sep_f32(A, stream));
+}
+
+template <typename TC>
+static int run_generic(cs_ctx* ctx, cs::CorrArgs<TC>& A, hipStream_t stream)
+{
+    int tw, th, rc;
+    ctx->last_kernel = CS_KERNEL_GENERIC;
+    cs::corr_generic_tile(A.km, A.kn, &tw, &th);
+    fill_grid(A, tw, th);
+    if constexpr (sizeof(TC) == 4) rc = cs::launch_corr_generic_f32(A, stream);
+    else rc = cs::launch_corr_generic_f64(A, stream);
+    return map_result(ctx, A.km, A.kn, rc);
+}
+
+// THE POLICY of float32 calls: the first route that is wanted and does not decline serves the call.
+template <>
+int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+{
+    const DispatchSwitches sw = read_dispatch_switches();
+    const bool fast = !sw.force_generic;
+    int rc;
     A.n_cu = ctx->n_cu;
     A.grid_cap = ctx->grid_cap;
     A.reg_mode = 0;
-    // truncated-SVD templates of low rank: row and column passes (maps; a layout or call form the kernel does not take returns -5 / -6
-    // before anything is launched, and the call goes on below)
-    if (allow_fast && lowrank_wanted(A)) {
-        rc = cs::launch_corr_lowrank_f32(A, stream);
-        if (rc == 0) {
-            ctx->last_kernel = CS_KERNEL_LOWRANK;
-            return CS_OK;
-        }
-        if (rc != -3 && rc != -5 && rc != -6) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    // per-bin masks on the matrix cores: the factorised mask tables + the persistent tile kernel
-    // (candidate mode without a sink -- the map fallback of find_candidates -- runs on the kernels that decide the screen
-    // at run time: the tile kernel's candidate instance has no map output)
-    if (allow_fast && mfma_reg_wanted(A) && !(A.ks.cand_cmin > 0.0f && !A.cand_keys)) {
-        if (A.out.layout == CS_LAYOUT_BAND) {
-            A.out_lo = A.out.band_lo;
-            A.out_hi = A.out.band_lo + A.out.band_w - 1;
-        } else {
-            A.out_lo = -(1 << 30);
-            A.out_hi = (1 << 30);
-        }
-        if (A.cand_keys) {                   // candidate sink: only the scanned diagonals (the map path trims in the compaction)
-            A.out_lo = std::max(A.out_lo, A.cand_dlo);
-            A.out_hi = std::min(A.out_hi, A.cand_dhi);
-        }
-        // (the mirrored-row instance of the tile kernel forms the corrections of the edge diagonals itself: no records)
-        const bool rim_in_kernel = A.w_sym && A.km == 17 && A.kn == 17 && !std::getenv("CHROMOSIGHT_HIP_MFMA_NORSYM");
-        rc = prepare_regular_mask<float>(ctx, A, A.km, stream, rim_in_kernel, true);
-        if (rc != CS_OK) return rc;
-        if (A.reg_mode == 1 && A.sig_is_f64) {
-            // float64 container (the pipeline keeps the detrended band in float64 for the exact re-scoring of the
-            // candidates), float32 arithmetic: the rows the windows reach are rounded into context scratch -- what
-            // the streaming kernel does pixel by pixel -- 12 B of traffic per pixel for a kernel 1.3x faster
-            const int kh = (A.km - 1) / 2;
-            const int p_lo = std::max(0, A.row_begin - kh), p_hi = std::min(A.ms, A.row_end + (A.km - 1) - kh);
-            const int width = A.sig.layout == CS_LAYOUT_BAND ? A.sig.band_w : A.ns;
-            const long long ld = ((long long)width + 15) / 16 * 16;
-            rc = ensure_scratch(ctx, &ctx->d_narrow, &ctx->d_narrow_bytes, (size_t)(p_hi - p_lo) * (size_t)ld * 4);
-            if (rc != CS_OK) return rc;
-            const double* src = reinterpret_cast<const double*>(A.sig.ptr) + ((long long)p_lo - A.sig.row0) * A.sig.ld;
-            rc = cs::launch_narrow_rows(src, A.sig.ld, reinterpret_cast<float*>(ctx->d_narrow), ld, p_hi - p_lo, width, ctx->n_cu, stream);
-            if (rc != 0) return fail(ctx, CS_ERR_HIP, "narrowing kernel failed: %s", hipGetErrorString((hipError_t)rc));
-            A.sig.ptr = ctx->d_narrow;
-            A.sig.ld = ld;
-            A.sig.row0 = p_lo;
-            A.sig_is_f64 = 0;
-        }
-        if (A.reg_mode == 1) {
-            cs::MfmaWeights E;
-            rc = ensure_wfrag(ctx, stream, A.km, A.kn, &E);
-            if (rc != CS_OK) return rc;
-            int path = 0;
-            rc = cs::launch_corr_mfma_f32(A, E, stream, &path);
-            ctx->last_kernel = path == 3 ? CS_KERNEL_MFMA_LIST : path == 2 ? CS_KERNEL_MFMA_REG : CS_KERNEL_MFMA;
-            if (rc == -5) return CS_NEED_MAP;
-            if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-            if ((path == 2 || path == 3) && A.cand_keys) ctx->cand_fused = true;
-            return CS_OK;
-        }
-    }
+    // the mirrored-row instance of the masked tile kernel (decided here for prepare_regular_mask, the launcher and the multi-block launch)
+    A.mfma_rsym = A.w_sym && A.km == 17 && A.kn == 17 && !sw.mfma_norsym;
+    if (fast && lowrank_wanted(A, sw) && (rc = run_lowrank(ctx, A, stream)) != kNextRoute) return rc;
+    if (fast && mfma_reg_wanted(A, sw) && (rc = run_mfma_reg(ctx, A, sw, stream)) != kNextRoute) return rc;
     if (A.sig.counts) return fail(ctx, CS_ERR_UNSUPPORTED, "a band of counts (CS_LAYOUT_BAND_COUNTS) is read by the masked float32 tile kernel only: per-bin masks, full mode, odd square template of up to 17");
-    if (!A.out.ptr && allow_fast && mfma_wide_wanted(A) && !A.w_rank1) {
-        // candidate sink without a map, template side 18 .. 33: the two-pass kernel appends the candidates itself
-        cs::MfmaWideWeights E;
-        rc = ensure_wfrag_wide(ctx, stream, A.km, A.kn, &E);
-        if (rc != CS_OK) return rc;
-        ctx->last_kernel = CS_KERNEL_MFMA_WIDE;
-        rc = cs::launch_corr_mfma_wide_f32(A, E, stream);
-        if (rc == -5) return CS_NEED_MAP;
-        if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        ctx->cand_fused = true;
-        return CS_OK;
-    }
-    if (allow_fast && mfma_large_wanted(A)) {
-        // template side 34 .. 81: candidate sinks (the kernel appends the candidates itself; a tile list is walked as listed)
-        // and, under CHROMOSIGHT_HIP_LARGE=1, maps
-        cs::MfmaLargeWeights E;
-        rc = ensure_wfrag_large(ctx, stream, A.km, A.kn, &E);
-        if (rc != CS_OK) return rc;
-        const bool sink = !A.out.ptr;
-        ctx->last_kernel = CS_KERNEL_MFMA_LARGE;
-        rc = cs::launch_corr_mfma_large_f32(A, E, stream);
-        if (rc == -5) return CS_NEED_MAP;
-        if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        if (sink) ctx->cand_fused = true;
-        return CS_OK;
-    }
+    // candidate sinks without a map (outer products wait for the kernels of the map routes)
+    if (fast && !A.out.ptr && mfma_wide_wanted(A, sw) && !A.w_rank1) return run_mfma_wide(ctx, A, stream);
+    if (fast && mfma_large_wanted(A, sw)) return run_mfma_large(ctx, A, stream);
     if (!A.out.ptr) return CS_NEED_MAP;      // every other kernel writes a map
-    if (allow_fast && mfma_wanted(A)) {
-        if (A.sig_is_f64 && A.mask_mode == 0 && A.sig.layout == 0 && A.out.layout == 0 && !A.nobs.ptr) {
-            // float64 container, float32 arithmetic: narrow the rows the windows reach into context scratch
-            // (what the kernels do pixel by pixel anyway) so that the persistent tile kernel can stage them
-            const int kh = (A.km - 1) / 2;
-            const int p_lo = std::max(0, A.row_begin - kh), p_hi = std::min(A.ms, A.row_end + (A.km - 1) - kh);
-            const long long ld = ((long long)A.ns + 15) / 16 * 16;
-            const size_t bytes = (size_t)(p_hi - p_lo) * (size_t)ld * 4;
-            rc = ensure_scratch(ctx, &ctx->d_narrow, &ctx->d_narrow_bytes, bytes);
-            if (rc != CS_OK) return rc;
-            const double* src = reinterpret_cast<const double*>(A.sig.ptr) + ((long long)p_lo - A.sig.row0) * A.sig.ld;
-            rc = cs::launch_narrow_rows(src, A.sig.ld, reinterpret_cast<float*>(ctx->d_narrow), ld, p_hi - p_lo, A.ns, ctx->n_cu, stream);
-            if (rc != 0) return fail(ctx, CS_ERR_HIP, "narrowing kernel failed: %s", hipGetErrorString((hipError_t)rc));
-            A.sig.ptr = ctx->d_narrow;
-            A.sig.ld = ld;
-            A.sig.row0 = p_lo;
-            A.sig_is_f64 = 0;
-        }
-        cs::MfmaWeights E;
-        rc = ensure_wfrag(ctx, stream, A.km, A.kn, &E);
-        if (rc != CS_OK) return rc;
-        int dense_path = 0;
-        rc = cs::launch_corr_mfma_f32(A, E, stream, &dense_path);
-        ctx->last_kernel = dense_path == 1 ? CS_KERNEL_MFMA_DENSE : dense_path == 2 ? CS_KERNEL_MFMA_REG : dense_path == 3 ? CS_KERNEL_MFMA_LIST : CS_KERNEL_MFMA;
-    } else if (allow_fast && fast_compatible(A) && fast_available(A.km, A.kn, &K) && !std::getenv("CHROMOSIGHT_HIP_WIDE_ALL")) {
-        ctx->last_kernel = CS_KERNEL_STREAM;
-#ifdef CS_HAVE_FAST
-#define CS_CASE(KK)                          \
-    case KK:                                 \
-        cs::corr_fast_tile_k##KK(A.row_end - A.row_begin, A.ns, A.out.layout == 1 ? A.out.band_w : 0, ctx->n_cu, &tw, &th);  \
-        fill_grid(A, tw, th, false);         \
-        rc = prepare_regular_mask<float>(ctx, A, KK, stream); \
-        if (rc != CS_OK) return rc;          \
-        rc = cs::launch_corr_fast_f32_k##KK(A, stream); \
-        break;
-        switch (K) {
-            CS_CASE(7) CS_CASE(9) CS_CASE(11) CS_CASE(13) CS_CASE(15) CS_CASE(17)
-            default: rc = -1;
-        }
-#undef CS_CASE
-#else
-        rc = -1;
-#endif
-    } else if (allow_fast && A.w_rank1 && !A.xcorr_only && !std::getenv("CHROMOSIGHT_HIP_NO_SEPARABLE") &&
-               cs::corr_sep_fits(A.km, A.kn, A.mask_mode != 0) &&
-               !(mfma_wide_wanted(A) && A.out.layout == CS_LAYOUT_BAND && A.out.band_w >= 512 && !std::getenv("CHROMOSIGHT_HIP_SEPARABLE_FIRST"))) {
-        // (an outer product that also fits the two-pass matrix-core kernel: that one on wide bands -- measured on the
-        // 31 x 31 stripes, profiles/r06_template_kernels.txt: 1001 diagonals 5.40 vs 6.92 ms, 234 diagonals 0.577 vs 0.517)
-        // templates without an unrolled instance that are an outer product (31 x 31 stripes): separable sums
-        ctx->last_kernel = CS_KERNEL_SEPARABLE;
-        cs::corr_sep_tile(&tw, &th);
-        fill_grid(A, tw, th);
-        rc = cs::launch_corr_sep_f32(A, stream);
-    } else if (allow_fast && mfma_wide_wanted(A)) {
-        cs::MfmaWideWeights E;
-        rc = ensure_wfrag_wide(ctx, stream, A.km, A.kn, &E);
-        if (rc != CS_OK) return rc;
-        ctx->last_kernel = CS_KERNEL_MFMA_WIDE;
-        rc = cs::launch_corr_mfma_wide_f32(A, E, stream);
-    } else {
-        ctx->last_kernel = CS_KERNEL_GENERIC;
-        cs::corr_generic_tile(A.km, A.kn, &tw, &th);
-        fill_grid(A, tw, th);
-        rc = cs::launch_corr_generic_f32(A, stream);
-    }
-    if (rc == -3) return fail(ctx, CS_ERR_UNSUPPORTED, "template %dx%d needs more than 160 KiB of LDS", A.km, A.kn);
-    if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return CS_OK;
+    if (fast && mfma_wanted(A, sw)) return run_mfma(ctx, A, stream);
+    if (fast && stream_wanted(A, sw)) return run_stream(ctx, A, sw, stream);
+    if (fast && separable_wanted(A, sw)) return run_separable(ctx, A, stream);
+    if (fast && mfma_wide_wanted(A, sw)) return run_mfma_wide(ctx, A, stream);
+    return run_generic(ctx, A, stream);
 }
 
+// ... and of float64 calls
 template <>
-int launch_corr<double>(cs_ctx* ctx, cs::CorrArgs<double>& A, hipStream_t stream, bool allow_fast)
+int launch_corr<double>(cs_ctx* ctx, cs::CorrArgs<double>& A, hipStream_t stream)
 {
-    int K = 0, tw, th, rc;
+    const DispatchSwitches sw = read_dispatch_switches();
     if (A.sig.counts) return fail(ctx, CS_ERR_UNSUPPORTED, "a band of counts (CS_LAYOUT_BAND_COUNTS) is read by the masked float32 tile kernel only");
     A.n_cu = ctx->n_cu;
     A.grid_cap = ctx->grid_cap;
-    ctx->last_kernel = CS_KERNEL_GENERIC;
-    if (allow_fast && fast_compatible(A) && fast_available(A.km, A.kn, &K)) {
-        ctx->last_kernel = CS_KERNEL_STREAM;
-#ifdef CS_HAVE_FAST
-#define CS_CASE(KK)                          \
-    case KK:                                 \
-        cs::corr_fast_tile_k##KK(A.row_end - A.row_begin, A.ns, A.out.layout == 1 ? A.out.band_w : 0, ctx->n_cu, &tw, &th);  \
-        fill_grid(A, tw, th, false);         \
-        rc = prepare_regular_mask<double>(ctx, A, KK, stream); \
-        if (rc != CS_OK) return rc;          \
-        rc = cs::launch_corr_fast_f64_k##KK(A, stream); \
-        break;
-        switch (K) {
-            CS_CASE(7) CS_CASE(9) CS_CASE(11) CS_CASE(13) CS_CASE(15) CS_CASE(17)
-            default: rc = -1;
-        }
-#undef CS_CASE
-#else
-        rc = -1;
-#endif
-    } else {
-        cs::corr_generic_tile(A.km, A.kn, &tw, &th);
-        fill_grid(A, tw, th);
-        rc = cs::launch_corr_generic_f64(A, stream);
-    }
-    if (rc == -3) return fail(ctx, CS_ERR_UNSUPPORTED, "template %dx%d needs more than 160 KiB of LDS", A.km, A.kn);
-    if (rc != 0) return fail(ctx, CS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return CS_OK;
+    if (!sw.force_generic && stream_wanted(A, sw)) return run_stream(ctx, A, sw, stream);
+    return run_generic(ctx, A, stream);
 }
 
 int check_matrix(cs_ctx* ctx, const cs_matrix* m, const char* what, int ns)
@@ -1015,7 +1023,7 @@ int build_args(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const c
             return fail(ctx, CS_ERR_INVALID, "explicit mask is null");
     }
     const double* kconv = kernel->h_kernel_conv ? kernel->h_kernel_conv : kernel->h_kernel;
-    const bool want_sym = !std::getenv("CHROMOSIGHT_HIP_NO_SYMMETRY");
+    const bool want_sym = !read_dispatch_switches().no_symmetry;
     cs_ctx::TemplateCache& tc = ctx->tcache[sizeof(TC) == 8 ? 1 : 0];
     {
         std::vector<double> key;
@@ -1282,10 +1290,9 @@ void cs_ctx_destroy(cs_ctx* ctx)
     }
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
     if (ctx->d_tiles_started) (void)hipFree(ctx->d_tiles_started);
-    if (ctx->d_wfrag) (void)hipFree(ctx->d_wfrag);
+    for (WeightImage* img : {&ctx->wfrag, &ctx->wfrag_wide, &ctx->wfrag_large})
+        if (img->d) (void)hipFree(img->d);
     if (ctx->d_rim) (void)hipFree(ctx->d_rim);
-    if (ctx->d_wfrag_wide) (void)hipFree(ctx->d_wfrag_wide);
-    if (ctx->d_wfrag_large) (void)hipFree(ctx->d_wfrag_large);
     if (ctx->h_small) (void)hipHostFree(ctx->h_small);
     if (ctx->d_cand_cnt) (void)hipFree(ctx->d_cand_cnt);
     if (ctx->d_map) (void)hipFree(ctx->d_map);

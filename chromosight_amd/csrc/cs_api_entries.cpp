@@ -23,7 +23,6 @@ int cs_normxcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
         if (rc) return rc;
         if (out_nobs->dtype != CS_F32) return fail(ctx, CS_ERR_INVALID, "out_nobs must be float32");
     }
-    const bool allow_fast = getenv("CHROMOSIGHT_HIP_FORCE_GENERIC") == nullptr;
     if (ctx->range_check && signal && signal->d_ptr && kernel) {
         // the guard of cs_ctx_set_range_check: largest |pixel| of the rows this call reads (the reduction of
         // cs_normxcorr2_host's slabs), then CS_ERR_RANGE for a non-finite pixel or, in float32, a magnitude beyond 1e15
@@ -57,7 +56,7 @@ int cs_normxcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
         A.out = view_of(out_corr);
         A.out_is_f64 = out_corr->dtype == CS_F64;
         A.nobs = want_nobs ? view_of(out_nobs) : cs::MatView{nullptr, 0, 0, 0, 0, 0};
-        return launch_corr<double>(ctx, A, stream, allow_fast);
+        return launch_corr<double>(ctx, A, stream);
     } else if (p->compute_dtype == CS_F32) {
         cs::CorrArgs<float> A;
         rc = build_args<float>(ctx, stream, signal, kernel, p, &A);
@@ -65,7 +64,7 @@ int cs_normxcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
         A.out = view_of(out_corr);
         A.out_is_f64 = out_corr->dtype == CS_F64;
         A.nobs = want_nobs ? view_of(out_nobs) : cs::MatView{nullptr, 0, 0, 0, 0, 0};
-        return launch_corr<float>(ctx, A, stream, allow_fast);
+        return launch_corr<float>(ctx, A, stream);
     }
     return fail(ctx, CS_ERR_INVALID, "bad compute dtype");
 }
@@ -267,7 +266,8 @@ int cs_xcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, int32_t ms, i
     std::vector<double> w(3 * (size_t)kk, 0.0);
     for (int t = 0; t < kk; ++t) w[t] = h_weights[t];
     // exactly vertically symmetric weights: the folded chain of the streaming kernel applies
-    bool sym = !std::getenv("CHROMOSIGHT_HIP_NO_SYMMETRY");
+    const DispatchSwitches sw = read_dispatch_switches();
+    bool sym = !sw.no_symmetry;
     for (int r = 0; r < km / 2 && sym; ++r)
         for (int c = 0; c < kn; ++c)
             if (w[r * kn + c] != w[(km - 1 - r) * kn + c]) {
@@ -277,8 +277,7 @@ int cs_xcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, int32_t ms, i
     // plain cross-correlations carry no tsvd marker: the separable kernel of low-rank templates takes them only when forced
     // (CHROMOSIGHT_HIP_LOWRANK=1), with the factors of the weights as passed
     int lr = 0;
-    const char* lr_env = getenv("CHROMOSIGHT_HIP_LOWRANK");
-    if (compute_dtype == CS_F32 && lr_env && lr_env[0] == '1') {
+    if (compute_dtype == CS_F32 && sw.lowrank == 1) {
         std::vector<double> U, V, none;
         lr = factor_low_rank(h_weights, km, kn, 8, U, V);
         if (lr > 0) append_lowrank_table(w, km, kn, U, V, lr, none, none, 0);
@@ -303,7 +302,7 @@ int cs_xcorr2(cs_ctx* ctx, void* stream_, const cs_matrix* signal, int32_t ms, i
         A.w_sym = sym ? 1 : 0;                                            \
         A.w_lr = A.w_lrc = sizeof(TC) == 4 ? lr : 0;                      \
         A.w_lrb = 0;                                                      \
-        return launch_corr<TC>(ctx, A, stream, getenv("CHROMOSIGHT_HIP_FORCE_GENERIC") == nullptr); \
+        return launch_corr<TC>(ctx, A, stream);                           \
     }
     if (compute_dtype == CS_F64) CS_XC(double)
     if (compute_dtype == CS_F32) CS_XC(float)

@@ -65,7 +65,7 @@ int corr_candidates_f32(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal
         return fail(ctx, CS_ERR_INVALID, "candidate mode needs a sink or a map");
     }
     ctx->cand_fused = false;
-    return launch_corr<float>(ctx, A, stream, getenv("CHROMOSIGHT_HIP_FORCE_GENERIC") == nullptr);
+    return launch_corr<float>(ctx, A, stream);
 }
 
 // 1-D patterns (cs_foci_params.diag_only): the reference forces bin1 = bin2 AFTER shifting the coordinates by (kh, kw)

@@ -29,6 +29,18 @@
 
 constexpr int kBlkLanes = 6;        // streams a multi-block tile pass may use (the caller's + side streams)
 
+// The float16 head / tail Toeplitz fragments of the float32 weight sets, as one of the matrix-core kernels reads them: a grow-only
+// device image and what it was built from (cs_api.cpp ensure_wfrag*)
+struct WeightImage {
+    void* d = nullptr;
+    size_t bytes = 0;
+    std::vector<unsigned char> key;     // the float32 weights the image was built from
+    int km = 0, kn = 0;
+    float unscale[3] = {1.0f, 1.0f, 1.0f};
+    bool matches(int km_, int kn_, const std::vector<unsigned char>& key_) const { return km == km_ && kn == kn_ && key == key_; }
+    void commit(int km_, int kn_, const std::vector<unsigned char>& key_) { km = km_, kn = kn_, key = key_; }
+};
+
 struct cs_ctx {
     int device = 0;
     int n_cu = 0;
@@ -103,8 +115,9 @@ struct cs_ctx {
     // grow-only scratch for the mask tables of the streaming kernel (one call in flight per context)
     void* d_ws = nullptr;
     size_t d_ws_bytes = 0;
-    // matrix-core kernel: the float32 weight sets as float16 head / tail Toeplitz fragments
-    void* d_wfrag = nullptr;
+    // the matrix-core kernels' weight images, each with its own key: templates of up to 17 x 17 (cs_launch.h MfmaWeights), the
+    // two-pass kernel of up to 33 x 33 (MfmaWideWeights), the kernel of 34 .. 81 (MfmaLargeWeights)
+    WeightImage wfrag, wfrag_wide, wfrag_large;
     // cs_detect_foci_batch_templates: host tables of the call in flight (asynchronous mode), its virtual blocks and capacity
     std::vector<cs::CorrArgs<double>> nb_tab;
     std::vector<long long> nb_seg;
@@ -112,22 +125,7 @@ struct cs_ctx {
     int nb_pending = 0;
     long long nb_cap = 0;
     std::vector<char> stage_uploaded;   // cs_stage_blocks: the tables the staging scratch holds (skip the upload of identical ones)
-    void* d_rim = nullptr;          // rim tables of the mask weight sets (cs_launch.h MfmaWeights::rim), same key as d_wfrag
-    std::vector<unsigned char> wfrag_key;     // the float32 weights the image was built from
-    int wfrag_km = 0, wfrag_kn = 0;
-    float wfrag_unscale[3] = {1.0f, 1.0f, 1.0f};
-    // ... and for the two-pass kernel of the templates of up to 33 x 33 (cs_launch.h MfmaWideWeights), with its own key
-    void* d_wfrag_wide = nullptr;
-    size_t d_wfrag_wide_bytes = 0;
-    std::vector<unsigned char> wfrag_wide_key;
-    int wfrag_wide_km = 0, wfrag_wide_kn = 0;
-    float wfrag_wide_unscale[3] = {1.0f, 1.0f, 1.0f};
-    // ... and for the kernel of the templates of 34 .. 81 (cs_launch.h MfmaLargeWeights)
-    void* d_wfrag_large = nullptr;
-    size_t d_wfrag_large_bytes = 0;
-    std::vector<unsigned char> wfrag_large_key;
-    int wfrag_large_km = 0, wfrag_large_kn = 0;
-    float wfrag_large_unscale[3] = {1.0f, 1.0f, 1.0f};
+    void* d_rim = nullptr;          // rim tables of the mask weight sets (cs_launch.h MfmaWeights::rim), same key as wfrag
     int last_kernel = 0;     // cs_last_kernel()
     int range_check = 0;     // cs_ctx_set_range_check()
     bool cand_fused = false; // the last candidate-mode call appended its candidates itself (no map was written)
@@ -342,11 +340,20 @@ void append_lowrank_table(std::vector<double>& w, int km, int kn, const std::vec
 // that would serve the call writes maps (nothing was launched that matters: the caller allocates the map and calls again)
 constexpr int CS_NEED_MAP = 1000;
 template <typename TC>
-int launch_corr(cs_ctx* ctx, cs::CorrArgs<TC>& A, hipStream_t stream, bool allow_fast);
+int launch_corr(cs_ctx* ctx, cs::CorrArgs<TC>& A, hipStream_t stream);
 template <>
-int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream, bool allow_fast);
+int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream);
 template <>
-int launch_corr<double>(cs_ctx* ctx, cs::CorrArgs<double>& A, hipStream_t stream, bool allow_fast);
+int launch_corr<double>(cs_ctx* ctx, cs::CorrArgs<double>& A, hipStream_t stream);
+// The environment switches of kernel selection (CHROMOSIGHT_HIP_<NAME>), read together once per call -- per call,
+// because tests and tools flip them in-process.  A flag is true when its variable is set; the tri-state ones are 1 / 0 for a value
+// that starts with that digit and -1 otherwise (unset: the measured default).
+struct DispatchSwitches {
+    bool force_generic, no_mfma, no_wide, wide_all, no_large, no_separable, separable_first, no_regular_mask, full_mask_tables,
+        mfma_norsym, no_symmetry, debug;
+    int mfma, mfma_reg, large, lowrank;
+};
+DispatchSwitches read_dispatch_switches();
 // validation + template statistics + weight upload + argument block of one correlation call (cs_api.cpp)
 template <typename TC>
 int build_args(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const cs_kernel* kernel,

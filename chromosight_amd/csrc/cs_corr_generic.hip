@@ -113,7 +113,7 @@ static int launch_generic(const CorrArgs<TC>& A, hipStream_t stream)
     const int LH = GEN_TH + A.km - 1;
     const int LWP = (GEN_TW + A.kn - 1 + 3) & ~3;
     const size_t smem = (sizeof(TC) + 1) * (size_t)LH * LWP + 16;
-    if (smem > 160 * 1024) return -3;
+    if (smem > 160 * 1024) return kLaunchNoFit;
     auto kern = corr_generic_kernel<TC>;
     if (smem > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

@@ -485,11 +485,11 @@ int corr_mfma_large_passes(int kn) { return kn + 15 <= 64 ? 2 : 3; }
 
 int launch_corr_mfma_large_f32(CorrArgs<float>& A, const MfmaLargeWeights& E, hipStream_t stream)
 {
-    if (!corr_mfma_large_fits(A.km, A.kn)) return -3;
-    if (A.sig.counts || A.sig.layout == 2) return -6;      // (bands of counts / lazily evaluated bands: other readers)
-    if (!A.out.ptr && !(A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f)) return -5;      // a map, or a candidate sink
-    if (A.defer_args) return -5;                           // (argument tables of the multi-block launch: the 17 x 17 tile kernel only)
-    if (E.passes != corr_mfma_large_passes(A.kn)) return -3;
+    if (!corr_mfma_large_fits(A.km, A.kn)) return kLaunchNoFit;
+    if (A.sig.counts || A.sig.layout == 2) return kLaunchDeclined;      // (bands of counts / lazily evaluated bands: other readers)
+    if (!A.out.ptr && !(A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f)) return kLaunchNeedMap;      // a map, or a candidate sink
+    if (A.defer_args) return kLaunchNeedMap;                           // (argument tables of the multi-block launch: the 17 x 17 tile kernel only)
+    if (E.passes != corr_mfma_large_passes(A.kn)) return kLaunchNoFit;
     A.tile_w = A.tile_h = LG_T;
     A.tiles_y = (A.row_end - A.row_begin + LG_T - 1) / LG_T;
     if (A.out.layout == 1) {
@@ -513,7 +513,7 @@ int launch_corr_mfma_large_f32(CorrArgs<float>& A, const MfmaLargeWeights& E, hi
     if (!A.cand_tiles) A.cand_n_tiles = 0;
     const long long blocks = A.cand_tiles ? (long long)A.cand_n_tiles : (long long)A.tiles_x * A.tiles_y;
     if (blocks <= 0) return 0;
-    if (blocks > 0x7ffffff0LL) return -3;
+    if (blocks > 0x7ffffff0LL) return kLaunchNoFit;
     const bool masked = A.mask_mode != 0;
     typedef void (*kern_t)(const CorrArgs<float>, const MfmaLargeWeights);
     const kern_t k = masked ? (E.passes == 3 ? corr_mfma_large_kernel<true, 3> : corr_mfma_large_kernel<true, 2>)

@@ -18,7 +18,7 @@
 // float32 forms of cs_corr_large.hip (thresholds, missing_tol, n_obs, the candidate screen).  Outputs: maps (dense / band, n_obs),
 // plain cross-correlations (xcorr_only: the factors of the raw weights, signal terms only) and the candidate sink
 // (CorrArgs::cand_keys, the contract of cs_corr_large.hip).  Signals: dense and band layouts, float32 or float64.  Bands of counts and
-// lazily evaluated bands are refused (-6): the `--tsvd` calls of the pipeline pass neither (detect_block reads block.full(), a
+// lazily evaluated bands are refused (kLaunchDeclined): the `--tsvd` calls of the pipeline pass neither (detect_block reads block.full(), a
 // float64 band or dense map), and a refused call takes the other kernels.
 //
 // Weight table (float32, behind the three weight sets at A.w + 3 km kn): nt = 1 + ra + rb rows of kn row weights [1, va_j, vb_k],
@@ -259,16 +259,17 @@ bool corr_lowrank_supports(const CorrArgs<float>& A)
            A.kn <= 81 && lr_smem(A.km, A.kn, A.mask_mode != 0, 1) <= 160 * 1024;
 }
 
-// 0: launched; -3: the template is not one this kernel takes; -5: neither a map nor a candidate sink (or an argument table of the
-// multi-block tile launch is wanted); -6: a signal layout read by other kernels (bands of counts, lazily evaluated bands).
+// 0: launched; kLaunchNoFit: the template is not one this kernel takes; kLaunchNeedMap: neither a map nor a candidate sink (or an
+// argument table of the multi-block tile launch is wanted); kLaunchDeclined: a signal layout read by other kernels (bands of counts,
+// lazily evaluated bands).
 // Nothing is launched on a non-zero return, and A is left as it was.
 int launch_corr_lowrank_f32(const CorrArgs<float>& A_in, hipStream_t stream)
 {
-    if (!corr_lowrank_supports(A_in)) return -3;
-    if (A_in.sig.counts || A_in.sig.layout == 2) return -6;
-    if (A_in.defer_args) return -5;
+    if (!corr_lowrank_supports(A_in)) return kLaunchNoFit;
+    if (A_in.sig.counts || A_in.sig.layout == 2) return kLaunchDeclined;
+    if (A_in.defer_args) return kLaunchNeedMap;
     const bool sink = !A_in.out.ptr && A_in.cand_keys && A_in.cand_count && A_in.ks.cand_cmin > 0.0f;
-    if (!A_in.out.ptr && !sink) return -5;
+    if (!A_in.out.ptr && !sink) return kLaunchNeedMap;
     CorrArgs<float> A = A_in;
     A.tile_w = LR_TW;
     A.tile_h = LR_TH;
@@ -297,7 +298,7 @@ int launch_corr_lowrank_f32(const CorrArgs<float>& A_in, hipStream_t stream)
     A.cand_tiles = nullptr;
     A.cand_n_tiles = 0;
     if (A.tiles_x <= 0 || A.tiles_y <= 0) return 0;
-    if (A.tiles_y > 65535) return -3;
+    if (A.tiles_y > 65535) return kLaunchNoFit;
     const bool masked = A.mask_mode != 0;
     // planes per round: as many as keep two workgroups on a CU (80 KiB), else as many as fit one
     int nq = 4;
@@ -305,7 +306,7 @@ int launch_corr_lowrank_f32(const CorrArgs<float>& A_in, hipStream_t stream)
     if (nq == 1)
         for (nq = 4; nq > 1 && lr_smem(A.km, A.kn, masked, nq) > 160 * 1024;) --nq;
     const size_t smem = lr_smem(A.km, A.kn, masked, nq);
-    if (smem > 160 * 1024) return -3;
+    if (smem > 160 * 1024) return kLaunchNoFit;
     const void* kern = masked ? (const void*)corr_lowrank_kernel<true> : (const void*)corr_lowrank_kernel<false>;
     if (smem > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

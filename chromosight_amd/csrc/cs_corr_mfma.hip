@@ -824,7 +824,7 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
     }
     const long long blocks = (long long)A.tiles_x * A.tiles_y;
     if (blocks <= 0) return 0;
-    if (blocks > 0x7fffffffLL) return -3;
+    if (blocks > 0x7fffffffLL) return kLaunchNoFit;
     const bool masked = A.mask_mode != 0;
     const bool dense_f32 = !masked && A.sig.layout == 0 && A.out.layout == 0 && !A.sig_is_f64 && !A.nobs.ptr && A.ms > 0 && A.ns > 0;
     // per-bin masks with the factorised tables in place (cs_api.cpp prepare_regular_mask), square template
@@ -922,28 +922,28 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
             // streaming kernel
             if ((D.band_in ? D.bw_in : D.ns) < 4) {
                 *dense_path = 0;
-                return -4;
+                return kLaunchNarrowRows;
             }
             *dense_path = 2;
-            const bool rsym = A.w_sym && A.km == 17 && A.kn == 17 && !getenv("CHROMOSIGHT_HIP_MFMA_NORSYM");
+            const bool rsym = A.mfma_rsym != 0;
             // candidate mode: the CAND instances append candidate coordinates to the caller's list and write no map
             const bool cand = A.ks.cand_cmin > 0.0f;
             if (cand) {
-                if (!A.cand_keys || !A.cand_count) return -5;
+                if (!A.cand_keys || !A.cand_count) return kLaunchNeedMap;
                 D.out = A.cand_keys;
                 D.nobs = reinterpret_cast<float*>(A.cand_count);
                 D.ld_out = A.cand_cap;
                 D.row0_out = (long long)A.cand_tag;
             }
             if (A.defer_args) {
-                if (!cand) return -5;
+                if (!cand) return kLaunchNeedMap;
                 std::memcpy(A.defer_args, &D, sizeof(D));
                 if (A.defer_rsym) *A.defer_rsym = rsym ? 1 : 0;
                 return 0;
             }
             if (A.cand_tiles) {
                 // a tile list (cs_candidates_tiles, dense outputs only): the list instance walks its A.cand_n_tiles entries
-                if (!cand || D.band_out || D.by_cut != A.tiles_y) return -5;
+                if (!cand || D.band_out || D.by_cut != A.tiles_y) return kLaunchNeedMap;
                 *dense_path = 3;
                 D.n_tiles = A.cand_n_tiles;
                 if (D.n_tiles <= 0) return 0;
@@ -968,7 +968,7 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
             hipLaunchKernelGGL(kr, dim3((unsigned)grid_r), dim3(256), MFD_SMEM_REG + MFD_LAUNCH_EXTRA, stream, D);
             return (int)hipGetLastError();
         }
-        if (!A.out.ptr) return -5;
+        if (!A.out.ptr) return kLaunchNeedMap;
         // 16-byte pieces: the tile's first staged column (64 bx - kw) and the row length must be multiples
         // of 4 so that no piece straddles the matrix edge; the transfers themselves need only 4-byte alignment
         // (checked bit for bit against 4-byte transfers at every misalignment), the 16-byte stores aligned rows
@@ -984,8 +984,8 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
         else hipLaunchKernelGGL((corr_mfma_dense_kernel<false, false>), dim3((unsigned)grid), dim3(256), (MFD_LAUNCH_EXTRA ? MFD_SMEM_REG + MFD_LAUNCH_EXTRA : MFD_SMEM), stream, D);
         return (int)hipGetLastError();
     }
-    if (A.sig.counts) return -6;                 // (a band of counts: only the masked tile kernel detrends what it reads)
-    if (!A.out.ptr) return -5;                   // (a candidate sink without a map: only the masked tile kernel serves that)
+    if (A.sig.counts) return kLaunchDeclined;                 // (a band of counts: only the masked tile kernel detrends what it reads)
+    if (!A.out.ptr) return kLaunchNeedMap;                   // (a candidate sink without a map: only the masked tile kernel serves that)
     const void* kern = masked ? (const void*)corr_mfma_kernel<true> : (const void*)corr_mfma_kernel<false>;
     hipError_t e = allow_big_lds(kern);
     if (e != hipSuccess) return (int)e;
@@ -1019,7 +1019,7 @@ int launch_corr_mfma_prepared(const void* h_arg, int rsym, int n_cu, int grid_ca
 // the copy is then done when the stream gets to the tile kernel instead of sitting between the staging and it.
 // (do_upload / launch: a caller that uploads on a side stream makes two calls -- upload only, then launch only; the caller's own
 // stream may be the null stream, so "no upload" is a flag and not a null handle)
-// the table's tile ranges (first[]) from its argument blocks: what an upload by somebody else needs in place (-3: too many tiles)
+// the table's tile ranges (first[]) from its argument blocks: what an upload by somebody else needs in place (kLaunchNoFit: too many tiles)
 int mfma_blocks_table_finish(void* h_table, int n_blocks)
 {
     int* first = reinterpret_cast<int*>(h_table);
@@ -1028,7 +1028,7 @@ int mfma_blocks_table_finish(void* h_table, int n_blocks)
     for (int b = 0; b < n_blocks; ++b) {
         first[b] = (int)total;
         total += args[b].n_tiles;
-        if (total > 0x7fffffffLL) return -3;
+        if (total > 0x7fffffffLL) return kLaunchNoFit;
     }
     first[n_blocks] = (int)total;
     return 0;
@@ -1038,15 +1038,9 @@ int launch_corr_mfma_blocks(void* h_table, void* d_table, int n_blocks, int rsym
                             bool do_upload, bool launch, unsigned* started, unsigned epoch)
 {
     if (n_blocks <= 0) return 0;
-    int* first = reinterpret_cast<int*>(h_table);
-    const MfmaDenseArgs* args = reinterpret_cast<const MfmaDenseArgs*>((char*)h_table + mfma_blocks_arg_offset(n_blocks));
-    long long total = 0;
-    for (int b = 0; b < n_blocks; ++b) {
-        first[b] = (int)total;
-        total += args[b].n_tiles;
-        if (total > 0x7fffffffLL) return -3;
-    }
-    first[n_blocks] = (int)total;
+    const int fit = mfma_blocks_table_finish(h_table, n_blocks);
+    if (fit != 0) return fit;
+    const long long total = reinterpret_cast<const int*>(h_table)[n_blocks];
     if (total == 0) return 0;
     hipError_t e = hipSuccess;
     if (do_upload) e = hipMemcpyAsync(d_table, h_table, mfma_blocks_table_bytes(n_blocks), hipMemcpyHostToDevice, upload);

@@ -194,12 +194,12 @@ __global__ __launch_bounds__(512) void corr_sep_kernel(const CorrArgs<float> A)
     }
 }
 
-// 0 on success, -3: the template needs more LDS than a CU has (the caller falls back to the runtime-size kernel)
+// 0 on success, kLaunchNoFit: the template needs more LDS than a CU has (the caller falls back to the runtime-size kernel)
 int launch_corr_sep_f32(const CorrArgs<float>& A, hipStream_t stream)
 {
     const bool masked = A.mask_mode != 0;
     const size_t smem = sep_smem(A.km, A.kn, masked);
-    if (smem > 160 * 1024) return -3;
+    if (smem > 160 * 1024) return kLaunchNoFit;
     const void* kern = masked ? (const void*)corr_sep_kernel<true> : (const void*)corr_sep_kernel<false>;
     if (smem > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

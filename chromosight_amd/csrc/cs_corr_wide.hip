@@ -893,10 +893,10 @@ bool corr_mfma_wide_fits(int km, int kn) { return km >= 1 && kn >= 1 && km <= 33
 
 int launch_corr_mfma_wide_f32(CorrArgs<float>& A, const MfmaWideWeights& E, hipStream_t stream)
 {
-    if (!corr_mfma_wide_fits(A.km, A.kn)) return -3;
-    if (A.sig.counts || A.sig.layout == 2) return -6;      // (bands of counts / lazily evaluated bands: other readers)
-    if (!A.out.ptr && !(A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f)) return -5;      // a map, or a candidate sink
-    if (A.defer_args) return -5;                           // (argument tables of the multi-block launch: the 17 x 17 tile kernel only)
+    if (!corr_mfma_wide_fits(A.km, A.kn)) return kLaunchNoFit;
+    if (A.sig.counts || A.sig.layout == 2) return kLaunchDeclined;      // (bands of counts / lazily evaluated bands: other readers)
+    if (!A.out.ptr && !(A.cand_keys && A.cand_count && A.ks.cand_cmin > 0.0f)) return kLaunchNeedMap;      // a map, or a candidate sink
+    if (A.defer_args) return kLaunchNeedMap;                           // (argument tables of the multi-block launch: the 17 x 17 tile kernel only)
     A.tile_w = A.tile_h = WD_T;
     A.tiles_y = (A.row_end - A.row_begin + WD_T - 1) / WD_T;
     if (A.out.layout == 1) {
@@ -917,7 +917,7 @@ int launch_corr_mfma_wide_f32(CorrArgs<float>& A, const MfmaWideWeights& E, hipS
     }
     const long long blocks = (long long)A.tiles_x * A.tiles_y;
     if (blocks <= 0) return 0;
-    if (blocks > 0x7ffffff0LL) return -3;
+    if (blocks > 0x7ffffff0LL) return kLaunchNoFit;
     const bool masked = A.mask_mode != 0;
     const bool two = A.kn > 17;
     typedef void (*kern_t)(const CorrArgs<float>, const MfmaWideWeights);

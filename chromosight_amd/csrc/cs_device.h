@@ -250,6 +250,8 @@ struct CorrArgs {
     const TC* fix_cols;
     int fix_top, fix_bot0, fix_width, fix_xband, fix_xlo, fix_side;
     int rim_in_kernel;       // edge mode without fix_lo / fix_hi records: the masked tile kernel forms them (MfmaWeights::rim)
+    int mfma_rsym;           // host side only (launch_corr decides, launch_corr_mfma_f32 picks the instance): the masked tile kernel's
+                             // mirrored-row instance serves the call
 };
 
 // ---------------------------------------------------------------------------------------

@@ -4,6 +4,14 @@
 
 namespace cs {
 
+// What a launcher returns: 0 launched, > 0 a hipError_t, < 0 nothing was launched because ...
+enum LaunchStatus : int {
+    kLaunchNoFit = -3,        // the template, the grid or the LDS the call needs does not fit this kernel
+    kLaunchNarrowRows = -4,   // the signal's rows hold fewer than the 4 values of a 16-byte staging piece
+    kLaunchNeedMap = -5,      // the call has neither a map nor a candidate sink this kernel can fill
+    kLaunchDeclined = -6,     // the signal's layout is read by other kernels (bands of counts, lazily evaluated bands)
+};
+
 // fast, fully unrolled square-template kernels (cs_corr_fast.hip, one object per size)
 #define CS_DECL_FAST(K)                                                        \
     int launch_corr_fast_f32_k##K(const CorrArgs<float>& A, hipStream_t s);    \

@@ -19,6 +19,7 @@
 
 #include <cstdlib>
 #include "cs_device.h"
+#include "cs_launch.h"
 #include "cs_launch_aux.h"
 
 namespace cs {
@@ -466,7 +467,7 @@ int launch_mask_prep_batch(const MaskPrepArgs<float>* args, const int* n_groups,
     for (int k = 0; k < n; ++k) {
         first[k] = (int)total;
         total += n_groups[k];
-        if (total > 0x7fffffffLL) return -3;
+        if (total > 0x7fffffffLL) return kLaunchNoFit;
     }
     first[n] = (int)total;
     if (total == 0) return no_launch();
