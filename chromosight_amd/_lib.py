@@ -184,10 +184,12 @@ class CsCall(C.Structure):
 CALL_STAGE_BLOCKS, CALL_EVENT_RECORD, CALL_STREAM_WAIT_EVENT, CALL_DETECT_FOCI_BLOCKS, CALL_DETECT_FOCI_BATCH_TEMPLATES, \
     CALL_ACCEPT_RECORDS, CALL_DETECT_FOCI_BATCH_FINISH, CALL_STREAM_WAIT_TILES = 1, 2, 3, 4, 5, 6, 7, 9
 
+STAGE_SMOOTH = 1                # cs_stage_blocks_opt flags (CS_STAGE_SMOOTH)
+
 # While a list is installed here, the entries named in _CAPTURED append (name, arguments) to it AFTER running as usual:
 # chromosight_amd/plan.py turns the calls of one genome step into a cs_run_calls list.
 CAPTURE = None
-_CAPTURED = ("cs_stage_blocks", "cs_event_record", "cs_stream_wait_event", "cs_detect_foci_blocks", "cs_detect_foci_batch_templates")
+_CAPTURED = ("cs_stage_blocks", "cs_stage_blocks_opt", "cs_event_record", "cs_stream_wait_event", "cs_detect_foci_blocks", "cs_detect_foci_batch_templates")
 
 
 # numpy view of an array of cs_focus records
@@ -252,6 +254,8 @@ _PROTOTYPES = {
     "cs_comm_allgather_rows_once": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "cs_comm_allreduce_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "cs_stage_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(CsStageBlock), C.c_int32, C.c_double]),
+    "cs_stage_blocks_opt": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(CsStageBlock), C.c_int32, C.c_double,
+                                      C.c_uint32]),
     "cs_csr_median": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_double)]),
     "cs_csr_median_many": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.c_int32, C.POINTER(C.c_double)]),
     "cs_ice_balance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32,

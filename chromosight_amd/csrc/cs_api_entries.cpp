@@ -680,7 +680,14 @@ int cs_csr_median_many(cs_ctx* ctx, void* stream_, const cs_csr* mats, int32_t n
 
 int cs_stage_blocks(cs_ctx* ctx, void* stream_, const cs_csr* genome, const cs_stage_block* blocks, int32_t n_blocks, double max_val)
 {
+    return cs_stage_blocks_opt(ctx, stream_, genome, blocks, n_blocks, max_val, 0);
+}
+
+int cs_stage_blocks_opt(cs_ctx* ctx, void* stream_, const cs_csr* genome, const cs_stage_block* blocks, int32_t n_blocks, double max_val,
+                        uint32_t flags)
+{
     CS_ENTER(ctx);
+    if (flags & ~(uint32_t)CS_STAGE_SMOOTH) return fail(ctx, CS_ERR_INVALID, "cs_stage_blocks_opt: unknown flags 0x%x", flags);
     cs::CsrView v;
     int rc = csr_view(ctx, genome, &v);
     if (rc) return rc;
@@ -718,6 +725,7 @@ int cs_stage_blocks(cs_ctx* ctx, void* stream_, const cs_csr* genome, const cs_s
         B.w64 = 0;
         B.counts = 0;
         B.lazy = nullptr;
+        B.smooth = (flags & CS_STAGE_SMOOTH) && s.n > 2;       // (preprocessing.py:189: blocks of more than 2 bins)
         if (s.band32_counts) {
             // CS_LAYOUT_BAND_COUNTS: d_band32 receives the raw counts (the caller vouches that they are exact in float32)
             if (B.dense || !s.d_band32 || (s.ld & 3) || s.ld < (int64_t)B.width + 4 || ((uintptr_t)s.d_band32 & 15) || s.d_band64 || s.f64_diags > 0)
@@ -794,7 +802,9 @@ int dispatch_call(cs_call& c)
     const int64_t* i = c.i;
     switch (c.fn) {
         case CS_CALL_STAGE_BLOCKS:
-            return cs_stage_blocks((cs_ctx*)p[0], p[1], (const cs_csr*)p[2], (const cs_stage_block*)p[3], (int32_t)i[0], c.d[0]);
+            // (i[1]: the flags of cs_stage_blocks_opt -- 0 in every list that holds a plain cs_stage_blocks)
+            return cs_stage_blocks_opt((cs_ctx*)p[0], p[1], (const cs_csr*)p[2], (const cs_stage_block*)p[3], (int32_t)i[0], c.d[0],
+                                       (uint32_t)i[1]);
         case CS_CALL_EVENT_RECORD:
             return cs_event_record((cs_ctx*)p[0], p[1], p[2]);
         case CS_CALL_STREAM_WAIT_EVENT:

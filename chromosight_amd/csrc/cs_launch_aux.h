@@ -773,6 +773,7 @@ struct StageBlock {
                              // bytes in front of it; `law` then holds n_diags values + the n_diags + 2 of their reciprocals); the
                              // tiler has nothing to write for such a block
     LazyBand* lazy;          // descriptor of the block's lazily evaluated float64 band, written by stage_finish_kernel (or null)
+    int smooth;              // 1: the law is replaced by its non-increasing least-squares fit (stage_smooth_kernel; --smooth-trend)
 };
 // what a LazyBand points to besides its block (the genome's pixel table)
 struct LazySource {

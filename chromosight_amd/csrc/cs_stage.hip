@@ -4,6 +4,8 @@
 //   stage_law_kernel     balance (count * w[bin1] * w[bin2]), slice the block, trim to the diagonals 0 .. keep, and
 //                        reduce the strictly positive pixels of every diagonal -- one pass over the pixel table
 //   stage_finish_kernel  law[d] = sum / count per block (0 for an empty diagonal)
+//   stage_smooth_kernel  --smooth-trend only (cs_stage_blocks_opt, CS_STAGE_SMOOTH): every block's law replaced by its
+//                        non-increasing least-squares fit, one workgroup per block, the law in LDS
 //   stage_tile_kernel    detrend by the law, >= max_val -> 1, NaN -> 0, and write the diagonal band (or the dense
 //                        map of a short chromosome) ONCE, in float64 (exact re-scoring, windows) and / or float32
 //                        (what the matrix-core tile kernel stages by LDS-DMA)
@@ -12,7 +14,8 @@
 // r holds the pixels (r, c >= r); the intra block of chromosome b is the prefix of every row up to its last bin, so a
 // "view" needs no copy and no binary search: a wave walks the row until the column leaves the band.
 //
-// Why these and not one launch chain per block (cs_aux.hip, still used for inter blocks, row windows, smoothing):
+// Why these and not one launch chain per block (cs_aux.hip, still used for inter blocks, row windows, blocks split over ranks,
+// laws of more than 4096 diagonals):
 // a genome is 23 blocks of 3 000 - 16 000 rows; per block the old chain is 4 launches that each under-fill the chip,
 // and its kernels were bound by latency, not by HBM (distance_law_kernel 1.25 TB/s: one dependent load chain per
 // wave and 16 waves per CU).  Here work is cut into groups of 128 rows of one block, workgroups take groups in
@@ -349,6 +352,117 @@ __global__ __launch_bounds__(kFinishDiags * kFinishPhases / PPT) void stage_fini
     }
 }
 
+// ---- --smooth-trend: isotonic (non-increasing) fit of every block's law (reference preprocessing.py:189-195) -----------
+// The input is the finished law with 0 on its empty diagonals (the reference zeroes the non-finite entries BEFORE the fit, so
+// the zeros take part in the pooling), unit weights, least squares: pool-adjacent-violators.  The reference fits all n
+// entries of the block, zeros behind the kept diagonals; a law is never negative, so a trailing zero never lies above what
+// precedes it and never pools: fitting the n_diags kept entries gives the same numbers.
+//
+// One workgroup per block, the law in LDS as a list of pools: sum and entries of a pool at its first entry (entries 0 = not
+// the start of a pool), and at its last entry the index of its first (to step backwards).  The fit is unique whatever the
+// order of the poolings, so every lane first pools a chunk of its own, then the chunk lists are merged pairwise: both halves
+// are monotone, only the pool that spans the seam can violate, and it grows to either side until it does not.  A single lane
+// running the textbook stack is up to 4096 dependent LDS round trips between the law pass and the tiler (CS_SMOOTH_LANES=1
+// builds that variant: DESIGN.md has both times).  Which additions form a pool's sum is fixed by n_diags alone (the chunks
+// and the merge tree are): the same bits on every run, no atomics.
+#ifndef CS_SMOOTH_LANES
+#define CS_SMOOTH_LANES 256
+#endif
+constexpr int kSmoothThreads = 256;
+constexpr int kSmoothLanes = CS_SMOOTH_LANES;
+static_assert(kSmoothLanes >= 1 && kSmoothLanes <= kSmoothThreads && (kSmoothLanes & (kSmoothLanes - 1)) == 0, "a power of two of lanes");
+
+// the lists of [a, seam) and [seam, b) -- each non-increasing -- become the list of [a, b)
+__device__ __forceinline__ void smooth_seam(double* sum, int* cnt, int* head, int a, int seam, int b)
+{
+    int ls = head[seam - 1], end = seam;                    // the pool [ls, end) that will span the seam
+    double s = sum[ls];
+    int c = end - ls;
+    for (;;) {
+        bool grew = false;
+        while (end < b) {                                   // mean(pool) < mean(next pool): s / c < s2 / c2
+            const double s2 = sum[end];
+            const int c2 = cnt[end];
+            if (c2 <= 0 || !(s * (double)c2 < s2 * (double)c)) break;      // (c2 > 0 always: `end` is the start of a pool)
+            cnt[end] = 0;
+            s += s2;
+            c += c2;
+            end += c2;
+            grew = true;
+        }
+        while (ls > a) {                                    // mean(previous pool) < mean(pool)
+            const int ps = head[ls - 1];
+            const double s0 = sum[ps];
+            const int c0 = ls - ps;
+            if (c0 <= 0 || !(s0 * (double)c < s * (double)c0)) break;
+            cnt[ls] = 0;
+            s = s0 + s;
+            c += c0;
+            ls = ps;
+            grew = true;
+        }
+        if (!grew) break;
+    }
+    sum[ls] = s;
+    cnt[ls] = c;
+    head[end - 1] = ls;
+}
+
+__global__ __launch_bounds__(kSmoothThreads) void stage_smooth_kernel(const StageBlock* __restrict__ blocks, int pitch)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const StageBlock B = blocks[blockIdx.x];
+    if (!B.smooth || B.n <= 2) return;                      // (uniform)
+    double* l_sum = reinterpret_cast<double*>(smem_raw);
+    int* l_cnt = reinterpret_cast<int*>(l_sum + pitch);
+    int* l_head = l_cnt + pitch;
+    int* s_last = l_head + pitch;                           // kSmoothThreads (no static LDS beside the 64 KB of a 4096-diagonal law)
+    const int n = B.n_diags, tid = threadIdx.x;
+    for (int d = tid; d < n; d += kSmoothThreads) {
+        l_sum[d] = B.law[d];
+        l_cnt[d] = 1;
+        l_head[d] = d;
+    }
+    __syncthreads();
+    const int chunk = (n + kSmoothLanes - 1) / kSmoothLanes;
+    const int a = min(n, tid * chunk), b = tid < kSmoothLanes ? min(n, a + chunk) : a;
+    for (int seam = a + 1; seam < b; ++seam) smooth_seam(l_sum, l_cnt, l_head, a, seam, seam + 1);
+    __syncthreads();
+    for (int w = chunk; w < n; w *= 2) {
+        const long long seam = (2ll * tid + 1) * w;
+        if (seam < n) smooth_seam(l_sum, l_cnt, l_head, (int)seam - w, (int)seam, (int)min((long long)n, seam + w));
+        __syncthreads();
+    }
+    // every entry's pool: the last pool start at or before it (a running maximum over the chunks' last starts)
+    int last = -1;
+    for (int d = a; d < b; ++d)
+        if (l_cnt[d] > 0) last = d;
+    s_last[tid] = last;
+    __syncthreads();
+    for (int o = 1; o < kSmoothThreads; o <<= 1) {
+        const int v = tid >= o ? s_last[tid - o] : -1;
+        __syncthreads();
+        s_last[tid] = max(s_last[tid], v);
+        __syncthreads();
+    }
+    int cur = tid > 0 ? s_last[tid - 1] : 0;
+    for (int d = a; d < b; ++d) {
+        if (l_cnt[d] > 0) cur = d;
+        l_head[d] = cur;
+    }
+    __syncthreads();
+    for (int d = tid; d < n; d += kSmoothThreads) {
+        const int p = l_head[d];
+        const double y = l_sum[p] / (double)l_cnt[p];       // (a pool of one entry: the entry itself, bit for bit)
+        B.law[d] = y;
+        if (B.counts) {                                     // what stage_finish_kernel derived from the unsmoothed law
+            const double ry = 1.0 / y;                      // (y = 0: infinity, then the cap -- as an empty diagonal)
+            B.law[B.n_diags + 1 + d] = ry;
+            reinterpret_cast<float*>(B.law + 2 * B.n_diags + 2)[1 + d] = (float)ry;
+        }
+    }
+}
+
 // A block's rows are written exactly once.  A wave builds its row in LDS -- zero it, scatter the detrended stored pixels
 // into their slots (slot = diagonal of a band, column of a dense block) -- and streams it out with 16-byte-per-lane
 // stores (1 KB per instruction, float64 and float32 copies from the same LDS row).  Writing gaps from the lane that holds
@@ -639,6 +753,14 @@ int enqueue_stage_blocks(const long long* indptr, const int* indices, const void
     else
         hipLaunchKernelGGL(stage_finish_kernel<1>, finish_grid, dim3(kFinishDiags * kFinishPhases), 0, stream, d_blocks, pitch, part_sum,
                            part_cnt, lazy_src);
+    bool any_smooth = false;
+    for (int b = 0; b < n_blocks; ++b) any_smooth = any_smooth || (h_blocks[b].smooth && h_blocks[b].n > 2);
+    if (any_smooth) {
+        const size_t smem_smooth = (sizeof(double) + 2 * sizeof(int)) * (size_t)pitch + sizeof(int) * kSmoothThreads;
+        if (smem_smooth > 48 * 1024)
+            (void)hipFuncSetAttribute((const void*)stage_smooth_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipLaunchKernelGGL(stage_smooth_kernel, dim3(n_blocks), dim3(kSmoothThreads), smem_smooth, stream, d_blocks, pitch);
+    }
     if (any_tiled) { CS_STAGE_BOTH(CS_STAGE_TILE, unroll_tile) }
 #undef CS_STAGE_BOTH
 #undef CS_STAGE_LAW_

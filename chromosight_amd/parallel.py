@@ -428,7 +428,7 @@ def stage_genome(genome, kernel_configs, owned=None, smooth=False, band_dtype=np
     dist, rank, world = _world()
     if lazy64 is None:
         from .engine import get_precision
-        lazy64 = (not smooth and not os.environ.get("CHROMOSIGHT_HIP_F64_TWIN") and get_precision() == "f32"
+        lazy64 = (not os.environ.get("CHROMOSIGHT_HIP_F64_TWIN") and get_precision() == "f32"
                   and np.dtype(band_dtype) == np.float64
                   and all(max(np.shape(k)) <= 17 for cfg in kernel_configs for k in cfg["kernels"]))
     dists = [max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs]
@@ -461,7 +461,9 @@ def stage_genome(genome, kernel_configs, owned=None, smooth=False, band_dtype=np
     # widest pattern is a band for a narrower one -- are staged for it here, on the genome's stream, instead of by the
     # host thread that will scan that configuration (detect_patterns: the thread would have to use the genome's context
     # beside the calling thread, and the templates of a 1-D pattern could not share one launch chain).
-    if hasattr(genome, "view_for") and not smooth:
+    # smooth: a fitted law depends on how many diagonals were fitted, so NO block is a view at another keep distance
+    # (view_for refuses) -- every configuration with a keep distance of its own gets its blocks staged here, one native call.
+    if hasattr(genome, "view_for"):
         extra_any = False
         for i in wide:
             need = []
@@ -596,17 +598,18 @@ def exchange_self_check():
 _PATTERN_THREADS = None
 
 
-def detect_patterns(genome, kernel_configs, owned=None, staged=None, tsvd=None, exchange=True):
+def detect_patterns(genome, kernel_configs, owned=None, staged=None, tsvd=None, exchange=True, smooth=False):
     """detect_genome for SEVERAL pattern configurations on blocks staged once (stage_genome), concurrently: a genome
     scan is a few bandwidth / matrix-core-bound launches (a 2-D pattern's tile kernels) next to many latency-bound ones
     (1-D patterns: a few thousand pixels per block and template; labelling, statistics, synchronisations) -- run one after
     the other the latter leave the chip idle, run side by side they disappear under the former.  One host thread per
     configuration whose templates are not iterated; the record exchanges then follow in configuration order on this
     thread (collectives must be issued in the same order on every rank), and so do iterated configurations as a whole.
+    smooth: --smooth-trend -- `staged` was staged with it (stage_genome(smooth=True)), and so is whatever a scan stages itself.
     Returns the list of detect_genome results."""
     global _PATTERN_THREADS
     if staged is None:
-        staged = stage_genome(genome, kernel_configs, owned=owned)
+        staged = stage_genome(genome, kernel_configs, owned=owned, smooth=smooth)
     dist, rank, world = _world()
     if owned is None:
         max_dist = max(max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs)
@@ -625,17 +628,17 @@ def detect_patterns(genome, kernel_configs, owned=None, staged=None, tsvd=None, 
     # the configuration that scans the widest band stays on this thread (a hand-over to a pool thread costs 50-100 us, and
     # its pass is the longest); the others go to the pool first
     here = max(side, key=lambda i: kernel_configs[i]["max_dist"]) if side else None
-    futures = {i: _PATTERN_THREADS.submit(detect_genome, genome, kernel_configs[i], tsvd=tsvd, owned=owned, staged=pick(i),
+    futures = {i: _PATTERN_THREADS.submit(detect_genome, genome, kernel_configs[i], tsvd=tsvd, owned=owned, staged=pick(i), smooth=smooth,
                                           exchange=False, exclusive=len(side) < 2, own_context=True)
                for i in side if i != here}
     local = {}
     if here is not None:
-        local[here] = detect_genome(genome, kernel_configs[here], tsvd=tsvd, owned=owned, staged=pick(here), exchange=False,
+        local[here] = detect_genome(genome, kernel_configs[here], tsvd=tsvd, owned=owned, staged=pick(here), smooth=smooth, exchange=False,
                                     exclusive=len(side) < 2)
     results = [None] * len(kernel_configs)
     for i, cfg in enumerate(kernel_configs):
         if i not in side:
-            results[i] = detect_genome(genome, cfg, tsvd=tsvd, owned=owned, staged=pick(i), exclusive=not side, exchange=exchange)
+            results[i] = detect_genome(genome, cfg, tsvd=tsvd, owned=owned, staged=pick(i), smooth=smooth, exclusive=not side, exchange=exchange)
     for i in side:                                           # (collectives in the same order on every rank)
         mine = local[i] if i in local else futures[i].result()
         # (exchange=False: this rank's records -- genome_step exchanges the configurations of a step together)
@@ -643,17 +646,18 @@ def detect_patterns(genome, kernel_configs, owned=None, staged=None, tsvd=None, 
     return results
 
 
-def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False):
+def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False, smooth=False):
     """One detect step of a sharded genome: stage_genome + detect_patterns, the results of detect_patterns.
     local=True: this process alone, whatever process group is initialised -- every block, no collective (pipeline.detect: a
     call one rank may make on its own, as the reference's detect is).  For the usual
     pair of configurations (a 2-D pattern and a 1-D pattern with several templates, single iterations) every step after the
     first is ONE native call on the arguments the first step used (chromosight_amd/plan.py: cs_run_calls) plus one record
-    exchange per configuration; anything else -- and any step whose call list reports an error -- takes the two calls."""
+    exchange per configuration; anything else -- and any step whose call list reports an error -- takes the two calls.
+    smooth: --smooth-trend (the laws fitted on the device by the staging call; a step of its own plan)."""
     if local:
         _LOCAL_DEPTH[0] += 1
         try:
-            return genome_step(genome, kernel_configs, owned=owned, tsvd=tsvd)
+            return genome_step(genome, kernel_configs, owned=owned, tsvd=tsvd, smooth=smooth)
         finally:
             _LOCAL_DEPTH[0] -= 1
     from . import plan as _plan
@@ -663,10 +667,10 @@ def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False):
         costs = [block_cost((genome.chrom_size(ci),) * 2, max_dist, False) for ci in range(genome.n_chrom)]
         owned = assign_blocks(costs, world)[rank]
     owned = list(owned)
-    if not owned or not _plan.plannable(genome, kernel_configs, tsvd):
-        staged = stage_genome(genome, kernel_configs, owned=owned)
-        return detect_patterns(genome, kernel_configs, owned=owned, staged=staged, tsvd=tsvd)
-    key = (tuple(owned), tuple((cfg["max_dist"], cfg["pearson"], cfg["max_perc_undetected"], cfg["max_perc_zero"],
+    if not owned or not _plan.plannable(genome, kernel_configs, tsvd, smooth=smooth):
+        staged = stage_genome(genome, kernel_configs, owned=owned, smooth=smooth)
+        return detect_patterns(genome, kernel_configs, owned=owned, staged=staged, tsvd=tsvd, smooth=smooth)
+    key = (tuple(owned), bool(smooth), tuple((cfg["max_dist"], cfg["pearson"], cfg["max_perc_undetected"], cfg["max_perc_zero"],
                                 tuple(np.asarray(k, dtype=np.float64).tobytes() for k in cfg["kernels"])) for cfg in kernel_configs))
     plans = genome.__dict__.setdefault("_step_plans", {})
     plan = plans.get(key)
@@ -678,10 +682,10 @@ def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False):
     from . import _lib
     _lib.CAPTURE = captured = []
     try:
-        staged = stage_genome(genome, kernel_configs, owned=owned)
+        staged = stage_genome(genome, kernel_configs, owned=owned, smooth=smooth)
         # (this rank's records, then the ONE exchange a replayed step makes too: whichever way a rank takes through a step --
         # a plan that outgrew its buffers falls back here -- the ranks issue the same collectives)
-        results = detect_patterns(genome, kernel_configs, owned=owned, staged=staged, tsvd=tsvd, exchange=False)
+        results = detect_patterns(genome, kernel_configs, owned=owned, staged=staged, tsvd=tsvd, exchange=False, smooth=smooth)
     finally:
         _lib.CAPTURE = None
     results = _exchange_records_many(results, kernel_configs)
@@ -731,10 +735,12 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
     mine = list(owned) if owned is not None else assign_blocks(costs, world)[rank]
     have = {}
     staged_in = staged
-    if staged is not None and not smooth:
+    if staged is not None:
         for ci in mine:
             blk = staged.get(ci)
-            if blk is None:
+            # (a block staged with the other kind of law is not this call's block; a smoothed one serves its own keep
+            # distance only: view_for refuses it)
+            if blk is None or bool(getattr(blk, "smooth", False)) != bool(smooth):
                 continue
             view = blk if (blk.max_dist == max_dist and blk.keep == min(max_dist, genome.chrom_size(ci)) + largest) \
                 else genome.view_for(blk, max_dist, largest)

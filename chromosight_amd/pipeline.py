@@ -21,7 +21,7 @@ import scipy.sparse as sp
 
 from . import engine
 from ._lib import (COUNTS_HEADER_BYTES, CS_F32, CS_F64, FOCUS_DTYPE, LAYOUT_BAND, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW, LAYOUT_BAND_LAZY,
-                   LAYOUT_BAND_PADDED, LAYOUT_DENSE, LAZY_BAND_BYTES, MASK_BINS, CsCsr, CsMatrix, CsStageBlock,
+                   LAYOUT_BAND_PADDED, LAYOUT_DENSE, LAZY_BAND_BYTES, MASK_BINS, STAGE_SMOOTH, CsCsr, CsMatrix, CsStageBlock,
                    get_device, np_dtype_code)
 from .utils import detection as cid
 from .utils import preprocessing as preproc
@@ -520,6 +520,7 @@ class DeviceCool:
             # are independent, and issuing them costs the host less than running them costs the GPU (23-block genome,
             # per step: 1 stream 12.8 ms, 2: 12.5, 4: 11.4-11.7, 6-12: 11.2)
             n_streams = min(6, len(chroms))
+            # (smooth here: what the one-call staging could not take -- the host fit between two copies, block after block)
             if n_streams <= 1 or options.get("reduce") is not None or options.get("smooth"):
                 return [self.stage_intra(ci, max_dist, largest_kernel, resident=True, **options) for ci in chroms]
             # process-wide like the worker pools: creating streams per DeviceCool cost 8 ms per `detect` on a small genome
@@ -551,8 +552,11 @@ class DeviceCool:
         """All the given chromosomes with ONE native call (cs_stage_blocks: three launches for the whole genome -- a
         pass over the pixel table for the distance laws, the laws' finish, and the detrend / tiler that writes every
         block once in float64 (exact re-scoring, windows) and float32 (what the matrix-core kernel stages)); None when
-        an option needs the block-by-block path (isotonic smoothing, a block split over ranks, float32-only bands)."""
-        if (smooth or reduce is not None or rows is not None or unused or not self.upper or not chroms
+        an option needs the block-by-block path (a block split over ranks, a law of more than 4096 diagonals, a pixel table
+        with a lower triangle).  smooth (--smooth-trend): one more launch fits every block's law on the device
+        (cs_stage_blocks_opt, CS_STAGE_SMOOTH) before anything is detrended by it; lazily evaluated bands and bands of raw
+        counts read the fitted law like any other."""
+        if (reduce is not None or rows is not None or unused or not self.upper or not chroms
                 or np.dtype(band_dtype) not in (np.dtype(np.float64), np.dtype(np.float32))):
             return None
         only32 = np.dtype(band_dtype) == np.float32       # float32 maps only (map-level callers: no exact re-scoring)
@@ -635,16 +639,21 @@ class DeviceCool:
             blk.buffer, blk.pool = (b32 if (only32 or b64 is None) else b64), self._free
             blk.buffer32 = None if (only32 or b64 is None) else b32
             blk.shared = shared                                 # (the law buffer of the call)
+            blk.d_law, blk.n_diags = laws + off - 8 * law_len[k], n_diags      # (the block's law in it: n_diags float64)
+            blk.smooth = bool(smooth)                           # (a fitted law serves its own keep distance only: view_for)
             if lazy[k]:
                 blk.genome = self                               # (the descriptor points into the pixel table)
-                blk.restage = (lambda ci=ci: self._restage_synced(ci, max_dist, largest_kernel, band_dtype=band_dtype))
+                blk.restage = (lambda ci=ci: self._restage_synced(ci, max_dist, largest_kernel, band_dtype=band_dtype, smooth=smooth))
             blocks.append(blk)
         genome = CsCsr(self.n_bins, self.n_bins, max(self.nnz, 1), self.indptr.ptr, self.indices.ptr, self.data.ptr,
                        np_dtype_code(self.val_dtype), 0, None, self.weight.ptr, self.weight.ptr)
         # asynchronous on `stream`: whoever reads the blocks on another stream or context synchronises first (the callers
         # that hand blocks to worker threads do; the law scratch is rewritten in stream order)
         with dev.lock:
-            dev._check(lib.cs_stage_blocks(dev.ctx, stream, C.byref(genome), table, len(geo), 10.0))
+            if smooth:
+                dev._check(lib.cs_stage_blocks_opt(dev.ctx, stream, C.byref(genome), table, len(geo), 10.0, STAGE_SMOOTH))
+            else:
+                dev._check(lib.cs_stage_blocks(dev.ctx, stream, C.byref(genome), table, len(geo), 10.0))
         return blocks
 
     def _restage_synced(self, ci, max_dist, largest_kernel, **options):
@@ -1393,15 +1402,15 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
     n_chrom = dcool.n_chrom
     max_dist = max(kernel_config["max_dist"] // binsize, 1)
     largest = max(np.shape(k)[0] for k in kernel_config["kernels"])
-    if not inter and not return_windows and not smooth and np.dtype(band_dtype) == np.float64 and dcool.upper and hasattr(dcool, "view_for"):
+    if not inter and not return_windows and np.dtype(band_dtype) == np.float64 and dcool.upper and hasattr(dcool, "view_for"):
         # ONE orchestration: the intra-chromosomal blocks of a plain `detect` go through the genome drivers bench.py times
         # (parallel.genome_step: blocks staged by one native call, batched chains, and -- for the configurations a StepPlan covers,
         # chromosight_amd/plan.py -- every call after the first on this DeviceCool as one native call list); the per-block
-        # machinery below keeps --inter, --smooth-trend and the runs that return windows.
+        # machinery below keeps --inter and the runs that return windows.
         from . import parallel
         # (local: `detect` is this process's call -- under an initialised process group it neither shards nor gathers; the sharded
         # driver is parallel.detect_genome / genome_step)
-        rec = parallel.genome_step(dcool, [kernel_config], tsvd=tsvd, local=True)[0]
+        rec = parallel.genome_step(dcool, [kernel_config], tsvd=tsvd, local=True, smooth=smooth)[0]
         if rec.shape[0] == 0:
             return pd.DataFrame(columns=OUTPUT_COLUMNS)
         first = np.asarray(off, dtype=np.int64)[rec[:, 0].astype(np.int64)]

@@ -28,6 +28,7 @@ def _device_pvalues():
 # argument slots of every entry: 'p' pointer, 'i' integer, 'd' double, in the order of the C prototype
 _SLOTS = {
     "cs_stage_blocks": (CALL_STAGE_BLOCKS, "ppppid"),
+    "cs_stage_blocks_opt": (CALL_STAGE_BLOCKS, "ppppidi"),      # (--smooth-trend: the flags travel in i[1], 0 for the plain entry)
     "cs_event_record": (CALL_EVENT_RECORD, "ppp"),
     "cs_stream_wait_event": (CALL_STREAM_WAIT_EVENT, "ppp"),
     "cs_detect_foci_blocks": (CALL_DETECT_FOCI_BLOCKS, "ppippppppipp"),
@@ -80,7 +81,9 @@ class StepPlan:
         by_name = {}
         for name, args, _thread in captured:
             by_name.setdefault(name, []).append(args)
-        stage, blocks, batch = (by_name.get(k, []) for k in ("cs_stage_blocks", "cs_detect_foci_blocks", "cs_detect_foci_batch_templates"))
+        blocks, batch = (by_name.get(k, []) for k in ("cs_detect_foci_blocks", "cs_detect_foci_batch_templates"))
+        stage_fn = "cs_stage_blocks_opt" if by_name.get("cs_stage_blocks_opt") else "cs_stage_blocks"
+        stage = by_name.get("cs_stage_blocks", []) + by_name.get("cs_stage_blocks_opt", [])
         want = (1, 1 if cfg2 is not None else 0, 1 if cfg1 is not None else 0)
         if (len(stage), len(blocks), len(batch)) != want:
             # (extra stagings -- short chromosomes staged dense for the wider pattern --, retries, block-by-block fall-backs)
@@ -186,7 +189,7 @@ class StepPlan:
             i_prep = k
             _fill(nxt(), *_SLOTS["cs_detect_foci_blocks"], prep, 2)
         i_stage = k
-        _fill(nxt(), *_SLOTS["cs_stage_blocks"], stage[0], 0)
+        _fill(nxt(), *_SLOTS[stage_fn], stage[0], 0)
         if cfg1 is not None:
             i_ready = k
             _fill(nxt(), *_SLOTS["cs_event_record"], rec_ev[-1], 0)
@@ -261,9 +264,11 @@ class StepPlan:
         return out
 
 
-def plannable(genome, kernel_configs, tsvd):
+def plannable(genome, kernel_configs, tsvd, smooth=False):
     """The configurations a StepPlan covers: a 2-D pattern with one square template (loops), a 1-D pattern with 1-4 templates of
-    one square size (borders, hairpins), or one of each; single iterations, no truncated SVD, the device pipeline."""
+    one square size (borders, hairpins), or one of each; single iterations, no truncated SVD, the device pipeline.
+    smooth (--smooth-trend) changes nothing here: the staging call of the list fits the laws (cs_stage_blocks_opt); a pair of
+    patterns then stages once per keep distance, and the StepPlan of such a step declines itself (more than one staging call)."""
     if tsvd is not None or not 1 <= len(kernel_configs) <= 2:
         return False
     if not (hasattr(genome, "view_for") and hasattr(genome, "dev") and hasattr(genome.dev, "pinned_empty")):

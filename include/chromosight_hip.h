@@ -333,6 +333,15 @@ typedef struct {
 #define CS_LAZY_BAND_BYTES 128
 int cs_stage_blocks(cs_ctx* ctx, void* stream, const cs_csr* genome, const cs_stage_block* blocks, int32_t n_blocks,
                     double max_val);
+/* cs_stage_blocks with options (flags 0: cs_stage_blocks itself, launch for launch).  CS_STAGE_SMOOTH: --smooth-trend -- the
+ * distance law of every block of more than 2 bins is replaced by its least-squares non-increasing fit (isotonic regression on
+ * unit weights over the law with 0 on its empty diagonals, preprocessing.py:189-195) before anything is detrended by it: one
+ * more launch between the laws' finish and the detrend / tiler pass, one workgroup per block.  d_law (and, for a band of counts,
+ * the reciprocals behind it) then hold the fitted law.  A fitted law depends on how many diagonals were kept: a block staged this
+ * way serves its own keep distance only. */
+enum { CS_STAGE_SMOOTH = 1 };
+int cs_stage_blocks_opt(cs_ctx* ctx, void* stream, const cs_csr* genome, const cs_stage_block* blocks, int32_t n_blocks,
+                        double max_val, uint32_t flags);
 
 /* Median of the stored values of a CSR view, NaN counted as 0 (np.nanmedian after the NaN -> 0 of
  * contacts_map.py:598-601 preprocess_inter_matrix, which divides an inter-chromosomal block by it).
@@ -568,7 +577,7 @@ int cs_candidates_tiles(cs_ctx* ctx, void* stream, const cs_matrix* signal, cons
  * integers in i[], doubles in d[] (chromosight_amd/plan.py builds them from the arguments of a step that ran the usual way
  * and replays them on the same buffers).  rc of every call is filled in; a lane stops at its first failing call; the
  * return value is the first non-zero rc (0: every call succeeded). */
-enum { CS_CALL_STAGE_BLOCKS = 1, CS_CALL_EVENT_RECORD = 2, CS_CALL_STREAM_WAIT_EVENT = 3, CS_CALL_DETECT_FOCI_BLOCKS = 4,
+enum { CS_CALL_STAGE_BLOCKS = 1 /* cs_stage_blocks_opt(p[0] .. p[3], i[0], d[0], flags = i[1]) */, CS_CALL_EVENT_RECORD = 2, CS_CALL_STREAM_WAIT_EVENT = 3, CS_CALL_DETECT_FOCI_BLOCKS = 4,
        CS_CALL_DETECT_FOCI_BATCH_TEMPLATES = 5, CS_CALL_ACCEPT_RECORDS = 6, CS_CALL_DETECT_FOCI_BATCH_FINISH = 7,
        CS_CALL_STREAM_WAIT_TILES = 9 /* cs_stream_wait_tiles(p[0], p[1], p[2], i[0], i[1]) */ };
 typedef struct {
