@@ -101,3 +101,37 @@ def normxcorr2_band(band, n, lo, width, kernel, r0, r1, out_lo, out_w, max_dist=
         C.c_int(r0), C.c_int(r1), C.c_int(out_lo), C.c_int(out_w), out.ctypes.data_as(dp), cond.ctypes.data_as(dp),
         C.c_int(n_threads))
     return out, cond
+
+
+def normxcorr2_points(signal, shape, kernel, rows, cols, band_lo=None, max_dist=None, sym_upper=False, full=True,
+                      miss_row=None, miss_col=None, missing_tol=0.75, kernel_conv=None, kernel_sq=None, n_threads=0):
+    """(corr, n_obs, cond, near) of the pixels (rows[t], cols[t]) of a map of `shape`: `signal` is the dense map
+    (band_lo None) or its diagonal band (signal[i, j - i - band_lo]).  near: a sum of the pixel lies within 1e-9
+    relative of a zeroing threshold (oracle.c pixel_near); cond is 1 where the
+    coefficient is 0 by rule (too few present pixels, or a template constant over the present ones).  The values of the map entries, bit for bit; a pixel
+    outside the map gets (0, km * kn, 1, False)."""
+    lib = load()
+    s = np.ascontiguousarray(signal, dtype=np.float64)
+    k = np.ascontiguousarray(kernel, dtype=np.float64)
+    kc = np.ascontiguousarray(kernel_conv, dtype=np.float64) if kernel_conv is not None else None
+    k2 = np.ascontiguousarray(kernel_sq, dtype=np.float64) if kernel_sq is not None else None
+    ms, ns = (int(x) for x in shape)
+    band = band_lo is not None
+    assert s.ndim == 2 and s.shape[0] == ms and (band or s.shape[1] == ns)
+    r = np.ascontiguousarray(rows, dtype=np.int32)
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    dp = C.POINTER(C.c_double)
+    ip = C.POINTER(C.c_int)
+    masked, mr, mc, pr, pc = _flags(miss_row, miss_col)
+    out, nobs, cond = np.empty(r.size), np.empty(r.size), np.empty(r.size)
+    near = np.zeros(r.size, dtype=np.uint8)
+    lib.oracle_normxcorr2_points(
+        s.ctypes.data_as(dp), C.c_int(ms), C.c_int(ns), C.c_longlong(s.shape[1]), C.c_int(int(band)),
+        C.c_int(int(band_lo or 0)), C.c_int(s.shape[1] if band else 0), k.ctypes.data_as(dp),
+        kc.ctypes.data_as(dp) if kc is not None else None, k2.ctypes.data_as(dp) if k2 is not None else None,
+        C.c_int(k.shape[0]), C.c_int(k.shape[1]), C.c_int(int(full)),
+        C.c_int(int(sym_upper)), C.c_int(-1 if max_dist is None else int(max_dist)), C.c_int(int(masked)), pr, pc,
+        C.c_double(missing_tol), r.ctypes.data_as(ip), c.ctypes.data_as(ip), C.c_longlong(r.size), out.ctypes.data_as(dp),
+        nobs.ctypes.data_as(dp), cond.ctypes.data_as(dp), near.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int(n_threads))
+    # a coefficient that is 0 by rule (oracle.c: bit 1) is well defined whatever its conditioning says
+    return out, nobs, np.where(near & 2, 1.0, cond), (near & 1).astype(bool)

@@ -10,6 +10,7 @@ Reference lines restated (relative to /root/reference/chromosight/):
   utils/preprocessing.py:129-197 distance_law: per diagonal, nanmean of the strictly positive pixels
                                  whose row and column bins are both detectable
   utils/preprocessing.py:256-310 detrend: divide by the law (NaN -> 0 first), values >= max_val -> 1
+  utils/preprocessing.py:189-195 smooth: non-finite law entries -> 0, then the closest non-increasing law (least squares)
 
 Pinned by tests/test_oracle_golden.py against the reference's own laws and prepared blocks
 (tests/golden/example_blocks.npz)."""
@@ -49,10 +50,28 @@ def distance_law_band(band, detectable):
     return law
 
 
-def prepare_band(band, detectable, max_val=10.0):
-    """Detrended, capped, NaN-free band (the matrix pattern_detector receives) and the law."""
+def isotonic_non_increasing(y):
+    """The non-increasing sequence closest to y in least squares, by pooling adjacent violators: a block whose mean
+    exceeds the mean of the block before it is merged into it."""
+    sums, counts = [], []
+    for v in np.asarray(y, dtype=np.float64):
+        sums.append(float(v))
+        counts.append(1)
+        while len(sums) > 1 and sums[-1] / counts[-1] > sums[-2] / counts[-2]:
+            s, c = sums.pop(), counts.pop()
+            sums[-1] += s
+            counts[-1] += c
+    return np.concatenate([np.full(c, s / c) for s, c in zip(sums, counts)])
+
+
+def prepare_band(band, detectable, max_val=10.0, smooth=False):
+    """Detrended, capped, NaN-free band (the matrix pattern_detector receives) and the law.  smooth: the law of the
+    diagonals 0 .. min(n, w) - 1, its gaps set to 0, replaced by its isotonic fit (a chromosome of 2 bins or fewer: not)."""
     n, w = band.shape
     law = distance_law_band(band, detectable)
+    if smooth and n > 2:
+        m = min(n, w)
+        law[:m] = isotonic_non_increasing(np.where(np.isfinite(law[:m]), law[:m], 0.0))
     y = np.where(np.isnan(law), 0.0, law)
     with np.errstate(all="ignore"):
         out = band / y[None, :]

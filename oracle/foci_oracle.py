@@ -11,9 +11,14 @@ Reference lines restated here (all in /root/reference/chromosight/utils/detectio
   pattern_detector :287-345   zero padding by (kh, kw) in full mode, NaN on the big_k first
                               sub-diagonals of intra maps, 1-D patterns forced on the diagonal
   validate_patterns:18-155    strict window bounds, missing bins -> NaN, zero / missing proportions
+  quantify mode    :233-238, 267-273, 277, 287-345 with coords given: nothing from a map not larger than the
+                              template, the score read from the diag-trimmed zero-eliminated map at the (kh, kw)-shifted
+                              coordinate of maps padded by (kw, kh), drop=False (NaN score + NaN window for an invalid
+                              position, :133-141), the p-value from the untrimmed map at the caller's coordinate
 
 Pinned by tests/test_oracle_golden.py against the reference's own outputs (tests/golden/nms.npz,
-example_blocks.npz) before it is trusted as the checker of the device path.
+example_blocks.npz) before it is trusted as the checker of the device path; quantify_table / quantify_table_band by
+tests/test_quantify_oracle.py (yeast_quantify.npz, example_blocks.npz, quantify_edges.npz).
 """
 import numpy as np
 from scipy import ndimage as ndi
@@ -56,10 +61,11 @@ def pick_foci_band(corr_band, lo, pearson, min_size=2):
     return foci
 
 
-def validate(coords, value_at, shape, miss_row, miss_col, kernel_shape, zero_tol, missing_tol, inter, full=True):
+def validate(coords, value_at, shape, miss_row, miss_col, kernel_shape, zero_tol, missing_tol, inter, full=True, stats=False):
     """Window statistics and validity of every pattern, as pattern_detector + validate_patterns do
     them.  value_at(p, q) -> contact value of matrix pixel (p, q) (vectorised, 0 when not stored).
-    coords: (n, 2) matrix coordinates (unpadded).  Returns (valid bool[n], windows[n, km, kn])."""
+    coords: (n, 2) matrix coordinates (unpadded).  Returns (valid bool[n], windows[n, km, kn]); with stats also a
+    dict of inside (the window passes the strict bounds, :99-104), n_zero and n_missing (:123-124; 0 where not inside)."""
     km, kn = kernel_shape
     kh, kw = (km - 1) // 2, (kn - 1) // 2
     half_h, half_w = km // 2 + 1, kn // 2 + 1
@@ -78,6 +84,7 @@ def validate(coords, value_at, shape, miss_row, miss_col, kernel_shape, zero_tol
     n = coords.shape[0]
     valid = np.zeros(n, dtype=bool)
     windows = np.full((n, km, kn), np.nan)
+    st = {"inside": np.zeros(n, dtype=bool), "n_zero": np.zeros(n, dtype=np.int64), "n_missing": np.zeros(n, dtype=np.int64)}
     for t in range(n):
         p1, p2 = int(coords[t, 0]) + sh_r, int(coords[t, 1]) + sh_c
         high, low = p1 - half_h + 1, p1 + half_h
@@ -95,13 +102,14 @@ def validate(coords, value_at, shape, miss_row, miss_col, kernel_shape, zero_tol
         tot = win.size
         n_zero = int(np.sum(win == 0))
         n_miss = int(np.sum(~np.isfinite(win)))
+        st["inside"][t], st["n_zero"][t], st["n_missing"][t] = True, n_zero, n_miss
         with np.errstate(all="ignore"):
             prop_undetected = n_miss / tot
             prop_zero = np.float64(n_zero) / np.float64(tot - n_miss)
         if prop_undetected < missing_tol and prop_zero < zero_tol:
             valid[t] = True
             windows[t] = win
-    return valid, windows
+    return (valid, windows, st) if stats else (valid, windows)
 
 
 def detect_table(matrix, corr_trimmed, miss_row, miss_col, kernel_shape, pearson, zero_tol, missing_tol,
@@ -155,3 +163,97 @@ def detect_table_band(band, band_lo, corr_band, out_lo, n, miss, kernel_shape, p
     valid, _ = validate(foci, value_at, (n, n), miss, miss, kernel_shape, zero_tol, missing_tol, False)
     keep = foci[valid]
     return np.column_stack([keep[:, 0], keep[:, 1], scores[valid]]).astype(np.float64)
+
+
+def _quantify(coords, value_at, coef_at, shape, miss_row, miss_col, kernel_shape, zero_tol, missing_tol, inter, max_dist,
+              full, diag_only):
+    """pattern_detector(coords=...) position by position.  coef_at(rows, cols) -> (coefficient, n_obs or None, cond,
+    near) of pixels of the UNTRIMMED coefficient map (0 / - / 1 / False outside it)."""
+    from oracle.pearson_oracle import corr_to_pval_oracle
+    km, kn = kernel_shape
+    coords = np.array(coords, dtype=np.int64).reshape(-1, 2)
+    n = coords.shape[0]
+    out = {"bin1": coords[:, 0].copy(), "bin2": coords[:, 1].copy(), "score": np.full(n, np.nan), "valid": np.zeros(n, dtype=bool),
+           "windows": np.full((n, km, kn), np.nan), "inside": np.zeros(n, dtype=bool), "n_zero": np.zeros(n, dtype=np.int64),
+           "n_missing": np.zeros(n, dtype=np.int64), "pvalue": np.full(n, np.nan), "n_obs": np.full(n, np.nan),
+           "cond": np.ones(n), "near": np.zeros(n, dtype=bool), "scanned": False}
+    if min(shape) <= max(km, kn):                       # :236-238: (None, None), the caller keeps its NaN
+        return out
+    out["scanned"] = True
+    shift = ((km - 1) // 2 - (kn - 1) // 2) if full else 0
+    if diag_only and not inter:                         # :314-315, after the (kh, kw) shift of :297-298
+        coords[:, 0] = coords[:, 1] - shift
+        out["bin1"] = coords[:, 0].copy()
+    valid, wins, st = validate(coords, value_at, shape, miss_row, miss_col, kernel_shape, zero_tol, missing_tol, inter,
+                               full=full, stats=True)
+    # the score: conv_mat[p1, p2] (:134) of the map padded by (kw rows, kh columns) at the coordinate shifted by (kh, kw)
+    sr, sc = coords[:, 0] + shift, coords[:, 1] - shift
+    kept = (sr >= 0) & (sr < shape[0]) & (sc >= 0) & (sc < shape[1])
+    if not inter:                                       # diag_trim(mat_conv, max_dist), :269-270: diagonals 0 .. max_dist
+        kept &= (sc - sr >= 0) & (sc - sr <= max_dist)
+    coef, _, cond, near = coef_at(sr, sc)
+    coef = np.where(np.isnan(coef), 0.0, coef)          # :267
+    out["score"] = np.where(valid, np.where(kept, coef, 0.0), np.nan)
+    out["cond"], out["near"] = np.where(kept, cond, 1.0), np.where(kept, near, False)
+    out["valid"], out["windows"] = valid, wins
+    out.update(st)
+    # the p-value: mat_log10_pvals[bin1, bin2] (:336-344) -- the untrimmed map, the caller's own coordinate; a pixel the
+    # sparse map does not store reads 0, that is p = 1
+    c0, nobs, _, _ = coef_at(coords[:, 0], coords[:, 1])
+    if nobs is not None:
+        c0 = np.where(np.isnan(c0), 0.0, c0)
+        with np.errstate(all="ignore"):
+            logp = np.where(c0 != 0, corr_to_pval_oracle(c0, nobs), 0.0)
+            out["pvalue"] = 10.0 ** logp
+        out["n_obs"] = np.asarray(nobs, dtype=np.float64)
+    return out
+
+
+def quantify_table(matrix, corr, coords, miss_row, miss_col, kernel_shape, zero_tol, missing_tol, inter=False, max_dist=None,
+                   n_obs=None, full=True, diag_only=False):
+    """Quantify mode on a dense test-sized map (intra or inter).  corr: the oracle's UNTRIMMED coefficient map (the trimming
+    to the diagonals 0 .. max_dist of an intra map is done here), or a callable (rows, cols) -> (coefficient, n_obs, cond,
+    near) such as c_oracle.normxcorr2_points; n_obs: the present-pixel counts of the map (p-values need them).  Returns a
+    dict of per-position arrays in input order: bin1, bin2, score (NaN when invalid, 0 outside the trimmed map), valid,
+    windows (NaN when invalid), inside, n_zero, n_missing, pvalue, n_obs, cond, near; scanned False when the map is not
+    larger than the template (everything NaN)."""
+    matrix = np.asarray(matrix, dtype=np.float64)
+    if callable(corr):
+        coef_at = corr
+    else:
+        corr = np.asarray(corr, dtype=np.float64)
+
+        def coef_at(r, c):
+            ok = (r >= 0) & (r < corr.shape[0]) & (c >= 0) & (c < corr.shape[1])
+            rr, cc = np.where(ok, r, 0), np.where(ok, c, 0)
+            nobs = None if n_obs is None else np.where(ok, np.asarray(n_obs)[rr, cc], float(kernel_shape[0] * kernel_shape[1]))
+            return np.where(ok, corr[rr, cc], 0.0), nobs, np.ones(r.size), np.zeros(r.size, dtype=bool)
+    return _quantify(coords, lambda p, q: matrix[p, q], coef_at, matrix.shape, miss_row, miss_col, kernel_shape, zero_tol,
+                     missing_tol, inter, max_dist, full, diag_only)
+
+
+def quantify_table_band(band, band_lo, corr_band, out_lo, n, coords, miss, kernel_shape, zero_tol, missing_tol, max_dist,
+                        n_obs_band=None, diag_only=False):
+    """The same for an intra map in band storage (band[i, j - i - band_lo]).  corr_band[i, j - i - out_lo]: the oracle's
+    coefficient band (what it does not hold reads 0), n_obs_band alike; or a callable as in quantify_table."""
+    band = np.asarray(band)
+    bw = band.shape[1]
+
+    def value_at(p, q):
+        x = q - p - band_lo
+        ok = (x >= 0) & (x < bw)
+        return np.where(ok, band[p, np.where(ok, x, 0)], 0.0)
+
+    if callable(corr_band):
+        coef_at = corr_band
+    else:
+        corr_band = np.asarray(corr_band, dtype=np.float64)
+
+        def coef_at(r, c):
+            x = c - r - out_lo
+            ok = (r >= 0) & (r < n) & (c >= 0) & (c < n) & (x >= 0) & (x < corr_band.shape[1])
+            rr, xx = np.where(ok, r, 0), np.where(ok, x, 0)
+            nobs = None if n_obs_band is None else np.where(ok, np.asarray(n_obs_band)[rr, xx], float(kernel_shape[0] * kernel_shape[1]))
+            return np.where(ok, corr_band[rr, xx], 0.0), nobs, np.ones(r.size), np.zeros(r.size, dtype=bool)
+    return _quantify(coords, value_at, coef_at, (n, n), miss, miss, kernel_shape, zero_tol, missing_tol, False, max_dist,
+                     True, diag_only)

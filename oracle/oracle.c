@@ -83,17 +83,21 @@ typedef struct {
     const double* kc2;
 } tmpl_t;
 
+static int near_thr(double x, double t) { return fabs(fabs(x) - t) <= 1e-9 * t; }
+
 /* one output pixel (i, j); *cond (optional) receives the conditioning of the quotient:
  * min(window variance / window mean square, present-template variance / template variance),
- * i.e. how far the two factors of the denominator are from an exactly degenerate window */
-static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, int j, double* nobs_out,
-                    double* cond_out)
+ * i.e. how far the two factors of the denominator are from an exactly degenerate window;
+ * *near (optional): bit 0 set when a sum of this pixel lies within 1e-9 relative of one of the zeroing thresholds (1e-4 on the
+ * window sums, 1e-10 on the denominator): there the last bits of a sum decide between a coefficient and 0 */
+static double pixel_near(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, int j, double* nobs_out,
+                         double* cond_out, int* near_out)
 {
     const int ms = g->ms, ns = g->ns, km = g->km, kn = g->kn, full = g->full, masked = g->masked;
     const int kh = (km - 1) / 2, kw = (kn - 1) / 2;
     const double n = T->n;
     double r = 0.0, nobs = n, cond = 1.0;
-    int zero = 0;
+    int zero = 0, cut_off = 0;
     if (!full) zero = (i < kh) || (i > ms - km + kh) || (j < kw) || (j > ns - kn + kw);
     if (g->sym_upper && (j - i) + (full ? (kn - km) : 0) < 0) zero = 1;
     if (!zero) {
@@ -115,6 +119,7 @@ static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, in
             }
         }
         double m1 = thr(s1), m2 = thr(s2), cz = thr(c), num, den;
+        int near = near_thr(s1, 1e-4) || near_thr(s2, 1e-4) || near_thr(c, 1e-4);
         double vs = m2 - m1 * m1, vk = T->kvar;
         if (!masked) {
             den = sqrt(m2 - m1 * m1) * T->kstd;
@@ -124,13 +129,14 @@ static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, in
             num = cz - m1 * T->kmean;
         } else {
             double np_ = n - nm;
+            near = near || near_thr(km_, 1e-4) || near_thr(k2m, 1e-4);
             double kmw = (T->ksum - thr(km_)) / np_;
             double k2mw = (T->k2sum - thr(k2m)) / np_;
             double m1w = m1 * n / np_, m2w = m2 * n / np_;
             double dd = (m2w - m1w * m1w) * T->kvar;
             dd = dd / T->kvar * (k2mw - kmw * kmw);
             den = sqrt(dd);
-            if (np_ < T->cut) den = 0.0;
+            if (np_ < T->cut) { den = 0.0; cut_off = 1; }
             double o = m1w * T->kmean;
             o = o * kmw * np_ / (T->kmean * n);
             num = (cz - o) * n / np_;
@@ -140,6 +146,7 @@ static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, in
             m2 = m2w;
         }
         r = (fabs(den) < 1e-10) ? 0.0 : num / den;
+        if (near_out) *near_out = near || near_thr(den, 1e-10);
         if (!isfinite(r)) r = 0.0;
         if (r < -1.0) r = -1.0;
         if (r > 1.0) r = 1.0;
@@ -148,11 +155,20 @@ static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, in
             double c1 = m2 > 0 ? vs / m2 : 1.0, c2 = T->kvar > 0 ? vk / T->kvar : 0.0;
             cond = c1 < c2 ? c1 : c2;
             if (!(cond == cond)) cond = 0.0;
+            /* bit 1 of *near: the denominator is 0 by rule, not by cancellation -- fewer present pixels than the cut (an
+             * integer comparison), or every present template entry equal (a two-valued template whose other value lies on
+             * missing pixels: its variance over the present ones is exactly 0) -- so the coefficient is 0 on every path */
+            if (near_out && (cut_off || (masked && vk == 0.0))) *near_out |= 2;
         }
     }
     if (nobs_out) *nobs_out = nobs;
     if (cond_out) *cond_out = cond;
     return r;
+}
+
+static double pixel(const geom_t* g, const sig_t* sg, const tmpl_t* T, int i, int j, double* nobs_out, double* cond_out)
+{
+    return pixel_near(g, sg, T, i, j, nobs_out, cond_out, NULL);
 }
 
 static void make_template(tmpl_t* T, const double* kernel, const double* kernel_conv, const double* kernel_sq,
@@ -266,6 +282,40 @@ int oracle_normxcorr2_band(const double* band, int n, long long ld, int lo, int 
             out_corr[(size_t)(i - r0) * out_w + x] = r;
             if (out_cond) out_cond[(size_t)(i - r0) * out_w + x] = cond;
         }
+    }
+    free(kc2);
+    return 0;
+}
+
+/*
+ * The coefficient, the present-pixel count and the conditioning of a LIST of pixels (rows[t], cols[t]) of a dense
+ * (band == 0, ld = ns) or banded (band != 0: lo, w as above) map: what quantify needs, without the whole map.
+ * A pixel outside the map gets 0 / km * kn / 1.  The same pixel() as the map entries: equal bit for bit.
+ */
+int oracle_normxcorr2_points(const double* sig, int ms, int ns, long long ld, int band, int lo, int w,
+                             const double* kernel, const double* kernel_conv, const double* kernel_sq, int km, int kn, int full,
+                             int sym_upper, int max_dist, int masked, const uint8_t* miss_row, const uint8_t* miss_col,
+                             double missing_tol, const int* rows, const int* cols, long long n_points, double* out_corr,
+                             double* out_nobs, double* out_cond, uint8_t* out_near, int n_threads)
+{
+    geom_t g = {ms, ns, km, kn, full, sym_upper, max_dist, masked, miss_row, miss_col};
+    sig_t sg = {sig, ld, band, lo, w};
+    tmpl_t T;
+    double* kc2 = (double*)malloc(sizeof(double) * km * kn);
+    make_template(&T, kernel, kernel_conv, kernel_sq, km, kn, missing_tol, kc2);
+#ifdef _OPENMP
+    if (n_threads > 0) omp_set_num_threads(n_threads);
+#pragma omp parallel for schedule(dynamic, 64)
+#endif
+    for (long long t = 0; t < n_points; ++t) {
+        const int i = rows[t], j = cols[t];
+        double r = 0.0, nobs = (double)km * kn, cond = 1.0;
+        int near = 0;
+        if (i >= 0 && i < ms && j >= 0 && j < ns) r = pixel_near(&g, &sg, &T, i, j, &nobs, &cond, &near);
+        out_near[t] = (uint8_t)near;   /* bit 0: near a threshold; bit 1: 0 by rule */
+        out_corr[t] = r;
+        out_nobs[t] = nobs;
+        out_cond[t] = cond;
     }
     free(kc2);
     return 0;

@@ -18,6 +18,7 @@ Reference lines restated (all relative to /root/reference/chromosight/utils/):
                            preprocessing.py:404-498 (frame_missing_mask)
   normxcorr2_oracle        detection.py:807-914, 917-1131 (sparse), 1134-1273 (dense)
   corr_to_pval_oracle      stats.py:43-81
+  tsvd_kernel_oracle       preprocessing.py:830-847 (factorise_kernel), as xcorr2 applies it (detection.py:618-619)
   distance_law_oracle      preprocessing.py:129-197
   detrend_oracle           preprocessing.py:256-310
 """
@@ -221,6 +222,20 @@ def corr_to_pval_oracle(corr, n_obs):
             continue
         p = math.erfc(-x / math.sqrt(2.0))  # 2 * Phi(x), x <= 0
         flat_o[idx] = math.log10(p) if p > 0 else -math.inf
+    return out
+
+
+def tsvd_kernel_oracle(kernel, prop_info=0.999):
+    """The template xcorr2 really correlates with under tsvd: the sum of the first k singular triplets, k the smallest
+    count whose squared singular values exceed prop_info of their total.  normxcorr2 passes the template, and its
+    square for the masked sums, through it separately (detection.py:1016, 1037-1043, 1082)."""
+    K = np.asarray(kernel, dtype=np.float64)
+    u, sigma, vt = np.linalg.svd(K)
+    energy = np.cumsum(sigma ** 2)
+    k = int(np.flatnonzero(energy > prop_info * energy[-1])[0]) + 1
+    out = np.zeros(K.shape)
+    for t in range(k):
+        out += sigma[t] * np.outer(u[:, t], vt[t])
     return out
 
 
