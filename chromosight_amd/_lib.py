@@ -263,6 +263,8 @@ _PROTOTYPES = {
     "cs_subsample": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32,
                                C.POINTER(CsSubsampleParams), C.POINTER(CsCsr), C.POINTER(C.c_int64), C.POINTER(CsSubsampleBlock),
                                C.c_void_p]),
+    "cs_coarsen": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
+                             C.POINTER(CsCsr), C.POINTER(C.c_int64)]),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

@@ -355,8 +355,11 @@ _WORKER_POOLS = {}
 _STAGE_STREAMS = {}            # per device object: (stream, extent scratch) pairs of DeviceCool.stage_blocks
 
 
+_PARENT = object()                  # DeviceCool.from_device_csr: "as the parent's"
+
+
 class DeviceCool:
-    """A decoded .cool resident in HBM.  cooler stores the upper triangle of the whole genome
+    """A decoded .cool resident in HBM. cooler stores the upper triangle of the whole genome
     sorted by (bin1, bin2): that table IS a CSR matrix (row pointer = searchsorted of bin1), so it
     is uploaded once -- counts, column bins, ICE weights -- and every sub-matrix is a view on it:
     balancing (count * w[bin1] * w[bin2], what cooler's matrix(balance=True) returns,
@@ -402,26 +405,34 @@ class DeviceCool:
         self._init_resident(weight)
 
     @classmethod
-    def from_device_csr(cls, parent, indptr, indices, data, nnz, val_dtype):
+    def from_device_csr(cls, parent, indptr, indices, data, nnz, val_dtype, *, offsets=_PARENT, binsize=_PARENT, bin_start=_PARENT,
+                        bin_end=_PARENT, weight=_PARENT):
         """A DeviceCool over a pixel table already in HBM (device buffers of the CSR: n_bins + 1 row pointers, column bins and
         counts, the first `nnz` entries used -- the result of subsample.subsample_csr), with `parent`'s bins, names and weights.
         The counts are non-negative integers: val_dtype is float32 when they are all below 2^24, as the constructor would
-        choose for an upload of the same table.  `.host` is downloaded once, when first read."""
+        choose for an upload of the same table.  `.host` is downloaded once, when first read.
+        offsets, binsize, bin_start, bin_end, weight: geometry and weights that differ from the parent's (a table of other bins:
+        coarsen.coarsen_csr); weight=None makes a table without weights.  The chromosomes and their names stay the parent's, and a
+        table whose pixels are the parent's regrouped by a monotone map of the bins is upper-triangle when the parent is."""
         self = cls.__new__(cls)
         self.dev = parent.dev
-        self.offsets = parent.offsets
-        self.n_bins = parent.n_bins
+        self.offsets = parent.offsets if offsets is _PARENT else np.asarray(offsets, dtype=np.int64)
+        if self.offsets.shape != parent.offsets.shape:
+            raise ValueError(f"{self.offsets.size} chromosome offsets for the parent's {len(parent.names)} chromosomes")
+        self.n_bins = int(self.offsets[-1])
         self.names = list(parent.names)
-        self.binsize = parent.binsize
-        self.bin_start, self.bin_end = parent.bin_start, parent.bin_end
+        self.binsize = parent.binsize if binsize is _PARENT else int(binsize)
+        self.bin_start = parent.bin_start if bin_start is _PARENT else bin_start
+        self.bin_end = parent.bin_end if bin_end is _PARENT else bin_end
         self.val_dtype = np.dtype(val_dtype).type
         self._counts_exact = self.val_dtype is np.float32
         self.nnz = int(nnz)
         self.indptr, self.indices, self.data = indptr, indices, data
-        self._host, self._host_weight = None, parent.host_weight
+        weight = parent.host_weight if weight is _PARENT else weight
+        self._host, self._host_weight = None, weight
         # a subset of an upper-triangle table is one; anything else is checked on the pixels
         self.upper = True if parent.upper else bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]))
-        self._init_resident(parent.host_weight)
+        self._init_resident(weight)
         return self
 
     def _init_resident(self, weight):
@@ -1009,6 +1020,15 @@ class DeviceCool:
         cool["bin1_id"], cool["bin2_id"], cool["count"] = b1[nz], b2[nz], new[nz]
         return DeviceCool(cool, self.dev)
 
+    def coarsened(self, factor):
+        """A DeviceCool of `factor` times the bin size, built on the device from this one's table (chromosight_amd/coarsen.py,
+        cs_coarsen): what `cooler coarsen -k factor` writes -- every chromosome's bins regrouped `factor` at a time on their own,
+        the stored pixels summed per coarse pixel, nothing mirrored.  The counts must be non-negative integers (ValueError
+        otherwise).  The result has no weights (fine-bin weights mean nothing for coarse bins): balance it (balance.ice_balance +
+        set_weights, or pipeline.open_cool(resolution=)).  factor 1 gives a table equal to this one, with its weights."""
+        from .coarsen import coarsen_device
+        return coarsen_device(self, factor)
+
     def bins_of(self, chroms, positions):
         """Whole-genome bin of (chromosome name, base pair) pairs; -1 outside the genome
         (HicGenome.coords_to_bins, contacts_map.py:404-450, for fixed-size bins)."""
@@ -1343,7 +1363,7 @@ def sub_matrices(dcool, inter):
     return [(a, b) for a in range(dcool.n_chrom) for b in range(dcool.n_chrom) if a == b or (a < b and inter)]
 
 
-def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None):
+def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None, resolution=None):
     """A .cool (path, `file.mcool::/resolutions/<binsize>`, or a decoded dictionary) resident on the device with the
     weights the reference's HicGenome.normalize gives it (contacts_map.py:182-229):
 
@@ -1354,7 +1374,13 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
     ICE runs with the reference's arguments (cooler.balance_cooler: cis_only = not inter, mad_max = n_mads, ignore_diags=2,
     min_nnz=10, max_iters=200; chromosight_amd/balance.py).  Unlike the reference, the new weights are NOT written back
-    into the input file.  The result goes to detect / quantify / detect_to_files and the parallel drivers."""
+    into the input file.  The result goes to detect / quantify / detect_to_files and the parallel drivers.
+
+    resolution: None, or the bin size in base pairs to work at, a positive multiple of the file's (ValueError otherwise).  A
+    larger one coarsens the uploaded table on the device (DeviceCool.coarsened: what `cooler coarsen` writes, which the reference
+    expects to have been run beforehand); the coarse table has no stored weights, so `norm` applies as to a file without any:
+    ICE on the coarse table for "auto" and "force", its detectable bins with weights 1.0 / NaN for "raw".  The file's own bin
+    size: as without the argument.  Every rank of a parallel run that coarsens its own copy gets the same table and weights."""
     if norm not in ("auto", "raw", "force"):
         raise ValueError("norm must be one of: auto, raw, force")
     if isinstance(uri_or_cool, (str, bytes)) or hasattr(uri_or_cool, "__fspath__"):
@@ -1362,10 +1388,19 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
         cool = cio._read_cool(uri_or_cool, balance)
     else:
         cool = dict(uri_or_cool)
-    weight = None if norm == "force" else cool.get("weight")
+    factor = 1
+    if resolution is not None:
+        binsize = int(cool["binsize"])
+        if isinstance(resolution, bool) or int(resolution) != resolution or resolution <= 0 or int(resolution) % binsize:
+            raise ValueError(f"resolution {resolution} is not a positive multiple of the file's bin size {binsize}")
+        factor = int(resolution) // binsize
+    # a coarsened table has no stored weights: the fine bins' mean nothing for the coarse ones
+    weight = None if norm == "force" or factor > 1 else cool.get("weight")
     raw = (lambda w: np.where(np.isfinite(np.asarray(w, dtype=np.float64)), 1.0, np.nan)) if norm == "raw" else (lambda w: w)
     cool["weight"] = None if weight is None else raw(weight)
     dcool = DeviceCool(cool, dev)
+    if factor > 1:
+        dcool = dcool.coarsened(factor)
     if weight is None:
         from .balance import ice_balance
         weight, _ = ice_balance(dcool, cis_only=not inter, mad_max=n_mads, ignore_diags=2, min_nnz=10, max_iters=200)

@@ -411,6 +411,21 @@ int cs_subsample(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t*
                  const cs_subsample_params* params, cs_csr* out, int64_t* h_out_nnz, cs_subsample_block* h_blocks,
                  int64_t* d_drawn);
 
+/* ---- coarsening of the resident pixel table: what `cooler coarsen -k factor` writes (the reference leaves this step to cooler,
+ * before chromosight is started) ----
+ * genome: the resident pixel table (square, plain row pointers, no weights, nnz < 2^31 - 1, columns sorted within every row).
+ * chrom_offsets: n_chrom + 1 host values from 0 to n_rows.  Every chromosome is regrouped on its own: one of n_c bins gets
+ * ceil(n_c / factor) coarse bins, coarse(b) = off'[c] + (b - off[c]) / factor, the last one possibly short.  The stored pixels are
+ * grouped by (coarse(bin1), coarse(bin2)) and summed; nothing is mirrored, so an upper-triangle table stays one.  Counts must be
+ * finite non-negative integers with a grand total below 2^53 (anything else: CS_ERR_INVALID), so every sum is exact and the
+ * result does not depend on the order of summation: it is bitwise the same for any launch shape, context or device (integer LDS
+ * atomics only, no float atomics).  factor < 1: CS_ERR_INVALID.
+ * out: caller-allocated d_indptr (coarse n_rows + 1 entries), d_indices and d_data with room for genome->nnz entries (8 bytes each
+ * in d_data); the call sets n_rows, n_cols, nnz (= *h_out_nnz) and dtype (CS_F32 when every sum is below 2^24, else CS_F64) and
+ * writes the pixels sorted by (bin1, bin2), without duplicates or zero entries.  Synchronous; the table is never written. */
+int cs_coarsen(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t* chrom_offsets, int32_t n_chrom, int32_t factor,
+               cs_csr* out, int64_t* h_out_nnz);
+
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
     double pearson;         /* candidate threshold: coefficient >= pearson and != 0 (detection.py:417-421) */
