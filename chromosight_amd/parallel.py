@@ -740,7 +740,7 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
             blk = staged.get(ci)
             # (a block staged with the other kind of law is not this call's block; a smoothed one serves its own keep
             # distance only: view_for refuses it)
-            if blk is None or bool(getattr(blk, "smooth", False)) != bool(smooth):
+            if blk is None or blk.smooth != bool(smooth):
                 continue
             view = blk if (blk.max_dist == max_dist and blk.keep == min(max_dist, genome.chrom_size(ci)) + largest) \
                 else genome.view_for(blk, max_dist, largest)

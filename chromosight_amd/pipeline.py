@@ -10,6 +10,7 @@ bin size); neither cooler nor h5py exists in this image.  The steps mirror the r
   post-processing       remove_neighbours, min_dist, NaN p-values, BH q-values
                         cli/chromosight.py:806-871
 """
+import collections
 import ctypes as C
 import os
 
@@ -183,6 +184,21 @@ def _pitch(width, quantum):
     return ld
 
 
+IntraGeometry = collections.namedtuple("IntraGeometry", "keep n_diags in_w out_w band ld")
+
+
+def intra_geometry(n, max_dist, largest_kernel):
+    """How an intra block of n bins is staged for a scanning distance and the largest template -- the ONE statement of it, which
+    _stage_fast, _stage_intra and view_for all read (a view stands in for a staging only while they agree).  keep: the
+    reference's keep distance; n_diags: the diagonals its law covers; in_w / out_w: the stored and the scanned band width;
+    band: the layout rule of the host path (_Staged) -- a band when it is less than half of the dense map; ld: the row pitch."""
+    keep = min(max_dist, n) + largest_kernel
+    in_w = min(keep, n - 1) + 1
+    out_w = min(max_dist, n - 1) + 1
+    band = 2 * max(in_w, out_w) < n
+    return IntraGeometry(keep, min(n, keep + 1), in_w, out_w, band, _pitch(in_w, 64) if band else _pitch(n, 16))
+
+
 class _FreeList:
     """Device buffers of released blocks, best fit first; every access under one lock (blocks are released by the
     garbage collector on whatever thread drops the last reference, taken by the staging threads)."""
@@ -221,9 +237,15 @@ class _Shared:
 _FULL_LOCK = threading.RLock()
 
 
+_BAND_LAYOUTS = (LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED)
+
+
 class StagedBlock:
-    """One sub-matrix staged in HBM (detrended band or dense map + the flags of its undetectable
-    bins): what pattern_detector works on after ContactMap.create_mat (contacts_map.py:453-526)."""
+    """One sub-matrix staged in HBM (detrended band or dense map + the flags of its undetectable bins): what pattern_detector works
+    on after ContactMap.create_mat (contacts_map.py:453-526).  Every field a staging route sets is declared below; any other name raises."""
+
+    __slots__ = ("name", "sig", "shape", "miss_row", "miss_col", "max_dist", "inter", "keep", "buffer", "pool", "row_window", "sig32", "restage",
+                 "_full", "buffer32", "shared", "d_law", "n_diags", "smooth", "genome", "parent", "view", "view_row0", "strip_pool")
 
     def __init__(self, name, sig, shape, miss_row, miss_col, max_dist, inter, keep):
         self.name, self.sig, self.shape = name, sig, shape
@@ -234,6 +256,19 @@ class StagedBlock:
         self.sig32 = None               # the same map in float32 (same layout), written by the same staging pass
         self.restage = None             # lazily evaluated float64 band (sig.layout == LAYOUT_BAND_LAZY): stages the block
         self._full = None               # again with the band stored, for the paths that read it themselves (full())
+        self.buffer32 = None            # the buffer of sig32 when the block owns one beside `buffer` (released with it)
+        self.shared = None              # one-call staging: the law / descriptor buffer every block of the call holds (_Shared)
+        self.d_law, self.n_diags = None, None       # ... and the block's law in it: n_diags float64
+        self.smooth = False             # detrended by a fitted law, which serves its own keep distance only (view_for)
+        self.genome = None              # the DeviceCool a lazily evaluated band's descriptor points into (kept alive)
+        self.parent = None              # view_for: the block whose buffers this view reads (kept alive; a view owns none)
+        self.view, self.view_row0 = None, None      # a row strip of a trans block: the cs_csr of its staged rows, their first row
+        self.strip_pool = None          # ... and the pool that owns its buffer (valid until the next strip is staged)
+
+    @property
+    def is_band(self):
+        """A whole banded intra block: what the batched native entries take (view_for also takes the two counts layouts)."""
+        return self.sig.layout in _BAND_LAYOUTS and not self.inter and self.row_window is None
 
     def full(self):
         """This block with its float64 band in memory.  The batched native entries read a lazily evaluated band through
@@ -255,7 +290,7 @@ class StagedBlock:
         try:
             if self.buffer is not None and self.pool is not None:
                 self.pool.release(self.buffer)
-                if getattr(self, "buffer32", None) is not None:
+                if self.buffer32 is not None:
                     self.pool.release(self.buffer32)
         except Exception:
             pass
@@ -301,7 +336,10 @@ _MAX_STRIP_ELEMENTS = (1 << 31) - 1
 
 
 def _inter_ld(n_c):
-    return (int(n_c) + 15) // 16 * 16             # (the row pitch of _stage_inter)
+    return (int(n_c) + 15) // 16 * 16             # (the row pitch of every staged trans block: the only place it is computed)
+
+
+_InterGeometry = collections.namedtuple("_InterGeometry", "s1 e1 s2 e2 n_r n_c ld")
 
 
 def plan_inter_strips(n_r, n_c, budget, halo, esz=8):
@@ -445,6 +483,7 @@ class DeviceCool:
             self.set_weights(weight)
         self._band = _Scratch(self.dev)
         self._ext = _Scratch(self.dev)
+        self._strips = _StripPool(self.dev)         # the row strips of trans blocks (allocates when the first one is staged)
         self._stage_lock = threading.RLock()
         self._free = _FreeList()        # HBM of released resident blocks, reused by the next staging
         self._workers = None
@@ -575,16 +614,10 @@ class DeviceCool:
         geo = []
         for ci in chroms:
             s, e = int(self.offsets[ci]), int(self.offsets[ci + 1])
-            n = e - s
-            keep = min(max_dist, n) + largest_kernel
-            n_diags = min(n, keep + 1)
-            if n_diags > 4096:
+            g = intra_geometry(e - s, max_dist, largest_kernel)
+            if g.n_diags > 4096:
                 return None
-            in_w = min(keep, n - 1) + 1
-            out_w = min(max_dist, n - 1) + 1
-            band = 2 * max(in_w, out_w) < n
-            ld = _pitch(in_w, 64) if band else _pitch(n, 16)
-            geo.append([ci, s, n, keep, n_diags, in_w, band, ld])
+            geo.append((ci, s, e - s, g))
         # lazy64: the float64 band of a banded block is NOT stored beyond its first `near` diagonals (where the runs of a
         # 1-D pattern live); the float64 kernels behind the batched entries recompute the few pixels they read from the
         # pixel table (include/chromosight_hip.h cs_stage_block: a third of the staging pass was writing that band).  The
@@ -592,7 +625,7 @@ class DeviceCool:
         # (lazy64 = "all": every diagonal stored AND a descriptor -- what tests/test_gpu_device_pipeline.py checks the recomputed
         # pixels against)
         near = 64
-        lazy = [bool(lazy64 and not only32 and g[6] and (lazy64 == "all" or g[5] > 2 * near)) for g in geo]
+        lazy = [bool(lazy64 and not only32 and g.band and (lazy64 == "all" or g.in_w > 2 * near)) for _, _, _, g in geo]
         # counts (default wherever the float64 band is lazily evaluated -- the detection path --; float32-only, map-level callers
         # ask for it): the float32 band of a banded block holds the RAW COUNTS, written by the pass that reduces the distance
         # law -- no detrend / tiler pass over the pixel table, no float64 near band; the tile kernel detrends the tiles it
@@ -604,21 +637,20 @@ class DeviceCool:
         if counts is None:
             counts = bool(lazy64) and lazy64 != "all"
         counts = bool(counts and self.counts_ok and not os.environ.get("CHROMOSIGHT_HIP_NO_COUNTS_BAND"))
-        cnt = [bool(counts and g[6] and (only32 or lazy[k])) for k, g in enumerate(geo)]
-        for k, g in enumerate(geo):
-            if cnt[k]:
-                g[7] = _pitch(g[5] + 4, 64)                     # (>= 4 zero slots behind every row's diagonals)
+        cnt = [bool(counts and g.band and (only32 or lazy[k])) for k, (_, _, _, g) in enumerate(geo)]
         # The laws (and the descriptors of lazily evaluated bands) live as long as the blocks do: one buffer per staging call,
         # held by every block of the call -- never the rewritten law scratch.  A recorded staging (plan.StepPlan replays the
         # cs_stage_blocks table verbatim, d_law included) must not point into a grow-only scratch that a later staging with a
         # longer law re-allocates (silent corruption on the next replay).
         # (counts: CS_COUNTS_LAW_BYTES -- the law, its reciprocals, float32 copies of the reciprocals and of the block's weights)
-        law_len = [(2 * g[4] + 2 + (g[4] + 3) // 2 + (g[2] + 1) // 2) if cnt[k] else g[4] for k, g in enumerate(geo)]
+        law_len = [(2 * g.n_diags + 2 + (g.n_diags + 3) // 2 + (n + 1) // 2) if cnt[k] else g.n_diags for k, (_, _, n, g) in enumerate(geo)]
         shared = _Shared(self._free, self._resident(8 * sum(law_len) + 256 + LAZY_BAND_BYTES * len(geo)))
         laws = shared.buffer.ptr + LAZY_BAND_BYTES * len(geo)
         table = (CsStageBlock * len(geo))()
         blocks, off = [], 0
-        for k, (ci, s, n, keep, n_diags, in_w, band, ld) in enumerate(geo):
+        for k, (ci, s, n, (keep, n_diags, in_w, _, band, ld)) in enumerate(geo):
+            if cnt[k]:
+                ld = _pitch(in_w + 4, 64)                       # (a band of raw counts: >= 4 zero slots behind every row's diagonals)
             near_k = in_w if lazy64 == "all" else near
             ld64 = (ld if lazy64 == "all" else _pitch(near, 2)) if lazy[k] else ld
             b64 = None if (only32 or cnt[k]) else self._resident(n * ld64 * 8)
@@ -686,15 +718,12 @@ class DeviceCool:
         view with fewer stored diagonals reads every pixel beyond them as 0 (diag_trim).  None when a view cannot stand in
         (dense-staged short chromosomes, row windows, a longer distance than the block holds)."""
         self._need_weights()
-        n = block.shape[0]
-        keep = min(max_dist, n) + largest_kernel
-        if (block.inter or block.sig.layout not in (LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW)
-                or getattr(block, "row_window", None) is not None
-                or block.keep is None or keep > block.keep or getattr(block, "smooth", False)):
+        keep, _, in_w, _, band, _ = intra_geometry(block.shape[0], max_dist, largest_kernel)
+        # (beside the layouts of StagedBlock.is_band, a view can be cut from the two bands of raw counts)
+        if (block.inter or block.sig.layout not in _BAND_LAYOUTS + (LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW)
+                or block.row_window is not None or block.keep is None or keep > block.keep or block.smooth):
             return None
-        in_w = min(keep, n - 1) + 1
-        out_w = min(max_dist, n - 1) + 1
-        if not 2 * max(in_w, out_w) < n:
+        if not band:
             return None                              # this pattern would have been staged dense: keep the layouts identical
         s = block.sig
         # (a narrower view of a zero-padded band is a plain band: the slots behind ITS diagonals hold the block's further ones)
@@ -751,39 +780,53 @@ class DeviceCool:
     @property
     def inter_high_water(self):
         """Largest number of device bytes the strip pool of trans blocks held (stage_inter(rows=...))."""
-        pool = getattr(self, "_strips", None)
-        return 0 if pool is None else pool.high_water
+        return self._strips.high_water
 
-    def _strip_pool(self):
-        if getattr(self, "_strips", None) is None:
-            self._strips = _StripPool(self.dev)
-        return self._strips
-
+    # The steps of trans staging, each written once: _stage_inter, _stage_inter_rows and stage_inter_many differ only in the rows
+    # they cover, where the buffer comes from, how the median is obtained and how many uploads they make.
     def _inter_geometry(self, ca, cb):
+        """The trans block (ca, cb): the genome bins of its rows s1 .. e1 and columns s2 .. e2, its shape and its row pitch."""
         s1, e1 = int(self.offsets[ca]), int(self.offsets[ca + 1])
         s2, e2 = int(self.offsets[cb]), int(self.offsets[cb + 1])
-        return s1, e1, s2, e2
+        return _InterGeometry(s1, e1, s2, e2, e1 - s1, e2 - s2, _inter_ld(e2 - s2))
+
+    def _inter_extent(self, geo, ra, rb, d_begin, d_end, stream):
+        """The extent pass over the rows ra .. rb - 1 of the block: their view (row r of the view = row ra + r of the block, the
+        columns of chromosome cb), bounded to the block's columns by the row extents written at d_begin / d_end."""
+        raw = self._view(geo.s1 + ra, geo.s1 + rb, geo.s2, geo.e2)
+        self.dev._check(self.dev.lib.cs_csr_band_extent(self.dev.ctx, stream, C.byref(raw), -geo.n_r, geo.n_c, d_begin, d_end))
+        return self._view(geo.s1 + ra, geo.s1 + rb, geo.s2, geo.e2, d_begin, d_end)
+
+    def _inter_whole_median(self, geo, ext, stream):
+        """(bounded view of the whole block, extents at `ext`; the median of its stored values)."""
+        view = self._inter_extent(geo, 0, geo.n_r, ext, ext + 8 * geo.n_r, stream)
+        med = C.c_double(0.0)
+        self.dev._check(self.dev.lib.cs_csr_median(self.dev.ctx, stream, C.byref(view), C.byref(med)))
+        return view, med.value
+
+    def _inter_scatter(self, view, d_law, n_law, ptr, dtype, ld, stream):
+        """The rows of `view` written dense at `ptr`: the "law" at d_law is the block's median on every diagonal, no cap --
+        value / median, NaN -> 0.  Returns the matrix written (row0 = 0: the scatter addresses the view's own rows)."""
+        sig = CsMatrix(ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0, 0)
+        self.dev._check(self.dev.lib.cs_csr_to_band(self.dev.ctx, stream, C.byref(view), d_law, n_law, 0.0, C.byref(sig)))
+        return sig
+
+    def _inter_block(self, ca, cb, geo, sig, name=None, own=None):
+        block = StagedBlock(name or f"{self.names[ca]}-{self.names[cb]}", sig, (geo.n_r, geo.n_c), _Ptr(self.miss.ptr + geo.s1),
+                            _Ptr(self.miss.ptr + geo.s2), None, True, None)
+        block.buffer, block.pool = own, self._free       # (own: the buffer the block hands back to the free list when it goes)
+        return block
 
     def inter_median(self, ca, cb, stream=None):
         """The median _stage_inter scales the trans block (ca, cb) by (cs_csr_median on the view of the whole block)."""
         self._need_weights()
         with self.dev.lock:
-            dev, lib = self.dev, self.dev.lib
-            s1, e1, s2, e2 = self._inter_geometry(ca, cb)
-            n_r, n_c = e1 - s1, e2 - s2
-            ext = self._ext.get(16 * n_r + 512)
-            d_begin, d_end = ext, ext + 8 * n_r
-            raw = self._view(s1, e1, s2, e2)
-            dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
-            view = self._view(s1, e1, s2, e2, d_begin, d_end)
-            med = C.c_double(0.0)
-            dev._check(lib.cs_csr_median(dev.ctx, stream, C.byref(view), C.byref(med)))
-            return med.value
+            geo = self._inter_geometry(ca, cb)
+            return self._inter_whole_median(geo, self._ext.get(16 * geo.n_r + 512), stream)[1]
 
     def _stage_inter_rows(self, ca, cb, rows, largest_kernel=None, median=None, name=None, stream=None, dtype=np.float64):
-        dev, lib = self.dev, self.dev.lib
-        s1, e1, s2, e2 = self._inter_geometry(ca, cb)
-        n_r, n_c = e1 - s1, e2 - s2
+        geo = self._inter_geometry(ca, cb)
+        n_r, n_c, ld = geo.n_r, geo.n_c, geo.ld
         a, b = int(rows[0]), int(rows[1])
         if not (0 <= a < b <= n_r):
             raise ValueError("row window outside the block")
@@ -792,28 +835,20 @@ class DeviceCool:
         halo = (int(largest_kernel) - 1) // 2
         ra, rb = _strip_rows(n_r, (a, b), halo)
         m = rb - ra
-        ld = _inter_ld(n_c)
         if m * ld > _MAX_STRIP_ELEMENTS:
             raise ValueError(f"a strip of {m} rows x {ld} is above 2^31 elements: cut the block into more strips")
         if median is None:
             median = self.inter_median(ca, cb, stream=stream)
         n_law = max(n_r, n_c)
         ext = self._ext.get(16 * m + 8 * n_law + 512)
-        d_begin, d_end, d_law = ext, ext + 8 * m, ext + 16 * m
-        # a view of the rows ra .. rb - 1 (row r of the view = row ra + r of the block), the columns of chromosome cb
-        raw = self._view(s1 + ra, s1 + rb, s2, e2)
-        dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
-        view = self._view(s1 + ra, s1 + rb, s2, e2, d_begin, d_end)
+        d_law = ext + 16 * m
+        view = self._inter_extent(geo, ra, rb, ext, ext + 8 * m, stream)
         scale = np.full(n_law, float(median))
-        dev._check(lib.cs_memcpy_h2d(dev.ctx, d_law, scale.ctypes.data, scale.nbytes, stream))
-        esz = np.dtype(dtype).itemsize
-        buf = self._strip_pool().take(m * ld * esz)
-        # (the scatter addresses the view's own rows; the block's matrix carries row0 = ra.  value / median, NaN -> 0, as _stage_inter)
-        dev._check(lib.cs_csr_to_band(dev.ctx, stream, C.byref(view), d_law, n_law, 0.0,
-                                      C.byref(CsMatrix(buf.ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0, 0))))
-        sig = CsMatrix(buf.ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0, ra)
-        block = StagedBlock(name or f"{self.names[ca]}-{self.names[cb]}", sig, (n_r, n_c), _Ptr(self.miss.ptr + s1),
-                            _Ptr(self.miss.ptr + s2), None, True, None)
+        self.dev._check(self.dev.lib.cs_memcpy_h2d(self.dev.ctx, d_law, scale.ctypes.data, scale.nbytes, stream))
+        buf = self._strips.take(m * ld * np.dtype(dtype).itemsize)
+        sig = self._inter_scatter(view, d_law, n_law, buf.ptr, dtype, ld, stream)
+        sig.row0 = ra                                    # (the block's matrix carries the strip's first row)
+        block = self._inter_block(ca, cb, geo, sig, name)
         block.row_window = (a, b)
         block.view, block.view_row0 = view, ra
         block.strip_pool = self._strips                  # (the pool owns the buffer; the strip is valid until the next staging)
@@ -836,12 +871,7 @@ class DeviceCool:
         lib = dev.lib
         s, e = int(self.offsets[ci]), int(self.offsets[ci + 1])
         n = e - s
-        keep = min(max_dist, n) + largest_kernel
-        n_diags = min(n, keep + 1)
-        in_w = min(keep, n - 1) + 1
-        out_w = min(max_dist, n - 1) + 1
-        # layout rule of the host path (_Staged): band when it is less than half of the dense map
-        band = 2 * max(in_w, out_w) < n
+        keep, n_diags, in_w, _, band, ld = intra_geometry(n, max_dist, largest_kernel)
         a, b = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
         if not (0 <= a < b <= n):
             raise ValueError("row window outside the block")
@@ -883,7 +913,6 @@ class DeviceCool:
             d_law = d_sum                                     # finished in place
             dev._check(lib.cs_distance_law_finish(dev.ctx, stream, d_sum, d_cnt, n_diags, d_law))
         esz = np.dtype(band_dtype).itemsize
-        ld = _pitch(in_w, 64) if band else _pitch(n, 16)
         # resident: the block owns its buffer (288 GB of HBM hold every block of a genome at once, so
         # blocks are staged once and reused by all templates / iterations); else a shared scratch
         buf = self._resident(m * ld * esz, dev) if resident else None
@@ -900,30 +929,18 @@ class DeviceCool:
     def _stage_inter(self, ca, cb, name=None, stream=None, resident=False, dtype=np.float64):
         """ContactMap.create_mat of a balanced inter-chromosomal block (ca < cb), on the device:
         NaN -> 0, divided by the median of its stored values (contacts_map.py:598-601), dense layout."""
-        dev, lib = self.dev, self.dev.lib
-        s1, e1 = int(self.offsets[ca]), int(self.offsets[ca + 1])
-        s2, e2 = int(self.offsets[cb]), int(self.offsets[cb + 1])
-        n_r, n_c = e1 - s1, e2 - s2
-        ext = self._ext.get(16 * n_r + 8 * max(n_r, n_c) + 512)
-        d_begin, d_end, d_law = ext, ext + 8 * n_r, ext + 16 * n_r
-        raw = self._view(s1, e1, s2, e2)
-        dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
-        view = self._view(s1, e1, s2, e2, d_begin, d_end)
-        med = C.c_double(0.0)
-        dev._check(lib.cs_csr_median(dev.ctx, stream, C.byref(view), C.byref(med)))
-        scale = np.full(max(n_r, n_c), med.value)
-        dev._check(lib.cs_memcpy_h2d(dev.ctx, d_law, scale.ctypes.data, scale.nbytes, stream))
-        esz = np.dtype(dtype).itemsize
-        ld = (n_c + 15) // 16 * 16
-        own = self._resident(n_r * ld * esz) if resident else None
-        ptr = own.ptr if resident else self._band.get(n_r * ld * esz)
-        sig = CsMatrix(ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0)
-        # "law" = the median on every diagonal, no cap: value / median, NaN -> 0
-        dev._check(lib.cs_csr_to_band(dev.ctx, stream, C.byref(view), d_law, scale.size, 0.0, C.byref(sig)))
-        block = StagedBlock(name or f"{self.names[ca]}-{self.names[cb]}", sig, (n_r, n_c), _Ptr(self.miss.ptr + s1),
-                            _Ptr(self.miss.ptr + s2), None, True, None)
-        block.buffer, block.pool = own, self._free
-        return block
+        geo = self._inter_geometry(ca, cb)
+        n_r, n_c, ld = geo.n_r, geo.n_c, geo.ld
+        n_law = max(n_r, n_c)
+        ext = self._ext.get(16 * n_r + 8 * n_law + 512)
+        d_law = ext + 16 * n_r
+        view, med = self._inter_whole_median(geo, ext, stream)
+        scale = np.full(n_law, med)
+        self.dev._check(self.dev.lib.cs_memcpy_h2d(self.dev.ctx, d_law, scale.ctypes.data, scale.nbytes, stream))
+        nbytes = n_r * ld * np.dtype(dtype).itemsize
+        own = self._resident(nbytes) if resident else None
+        ptr = own.ptr if resident else self._band.get(nbytes)
+        return self._inter_block(ca, cb, geo, self._inter_scatter(view, d_law, n_law, ptr, dtype, ld, stream), name, own)
 
     def stage_inter_many(self, pairs, dtype=np.float64, stream=None):
         """stage_inter(resident=True) for SEVERAL inter-chromosomal blocks: the extents of all of them, then their medians with
@@ -934,44 +951,30 @@ class DeviceCool:
             return []
         with self.dev.lock:
             dev, lib = self.dev, self.dev.lib
-            geo, total = [], 0
-            for ca, cb in pairs:
-                s1, e1 = int(self.offsets[ca]), int(self.offsets[ca + 1])
-                s2, e2 = int(self.offsets[cb]), int(self.offsets[cb + 1])
-                n_r, n_c = e1 - s1, e2 - s2
-                geo.append((ca, cb, s1, e1, s2, e2, n_r, n_c, total))
-                total += (16 * n_r + 511) // 256 * 256
-            # (the blocks' "laws" -- their median on every diagonal -- side by side behind the row extents: ONE upload)
-            law_off, laws = [], 0
-            for _, _, _, _, _, _, n_r, n_c, _ in geo:
+            geos = [self._inter_geometry(ca, cb) for ca, cb in pairs]
+            # (the blocks' row extents, then their "laws" -- their median on every diagonal -- side by side: ONE upload)
+            ext_off, total, law_off, laws = [], 0, [], 0
+            for geo in geos:
+                ext_off.append(total)
+                total += (16 * geo.n_r + 511) // 256 * 256
                 law_off.append(laws)
-                laws += (max(n_r, n_c) + 31) // 32 * 32
+                laws += (max(geo.n_r, geo.n_c) + 31) // 32 * 32
             ext = self._ext.get(total + 8 * laws + 512)
             views = (type(self._view(0, 1, 0, 1)) * len(pairs))()
-            for i, (ca, cb, s1, e1, s2, e2, n_r, n_c, off) in enumerate(geo):
-                d_begin, d_end = ext + off, ext + off + 8 * n_r
-                raw = self._view(s1, e1, s2, e2)
-                dev._check(lib.cs_csr_band_extent(dev.ctx, stream, C.byref(raw), -n_r, n_c, d_begin, d_end))
-                views[i] = self._view(s1, e1, s2, e2, d_begin, d_end)
+            for i, geo in enumerate(geos):
+                d_begin = ext + ext_off[i]
+                views[i] = self._inter_extent(geo, 0, geo.n_r, d_begin, d_begin + 8 * geo.n_r, stream)
             med = (C.c_double * len(pairs))()
             dev._check(lib.cs_csr_median_many(dev.ctx, stream, views, len(pairs), med))
-            out = []
-            esz = np.dtype(dtype).itemsize
             scale = np.empty(laws)
-            for i, (_, _, _, _, _, _, n_r, n_c, _) in enumerate(geo):
-                scale[law_off[i]:law_off[i] + max(n_r, n_c)] = med[i]
+            for i, geo in enumerate(geos):
+                scale[law_off[i]:law_off[i] + max(geo.n_r, geo.n_c)] = med[i]
             dev._check(lib.cs_memcpy_h2d(dev.ctx, ext + total, scale.ctypes.data, scale.nbytes, stream))
-            for i, (ca, cb, s1, e1, s2, e2, n_r, n_c, off) in enumerate(geo):
-                d_law = ext + total + 8 * law_off[i]
-                ld = (n_c + 15) // 16 * 16
-                own = self._resident(n_r * ld * esz)
-                sig = CsMatrix(own.ptr, np_dtype_code(dtype), LAYOUT_DENSE, ld, 0, 0)
-                # "law" = the median on every diagonal, no cap: value / median, NaN -> 0
-                dev._check(lib.cs_csr_to_band(dev.ctx, stream, C.byref(views[i]), d_law, max(n_r, n_c), 0.0, C.byref(sig)))
-                block = StagedBlock(f"{self.names[ca]}-{self.names[cb]}", sig, (n_r, n_c), _Ptr(self.miss.ptr + s1),
-                                    _Ptr(self.miss.ptr + s2), None, True, None)
-                block.buffer, block.pool = own, self._free
-                out.append(block)
+            out = []
+            for i, ((ca, cb), geo) in enumerate(zip(pairs, geos)):
+                own = self._resident(geo.n_r * geo.ld * np.dtype(dtype).itemsize)
+                sig = self._inter_scatter(views[i], ext + total + 8 * law_off[i], max(geo.n_r, geo.n_c), own.ptr, dtype, geo.ld, stream)
+                out.append(self._inter_block(ca, cb, geo, sig, own=own))
             return out
 
     def subsampled(self, sample, seed=0, inter=False, sampler="numpy"):
@@ -1055,7 +1058,7 @@ def detect_block(dcool, block, kernel_config, kernel, tsvd=None, coords=None, wa
     _check_template(kernel)
     kspec = engine.KernelSpec(kernel, tsvd)
     block = block.full() if hasattr(block, "full") else block     # (the per-block entries read the float64 band themselves)
-    if getattr(block, "row_window", None) is not None:
+    if block.row_window is not None:
         if coords is not None or all_gather is None:
             raise ValueError("a row window of a block needs detect mode and an all_gather")
         return cid.detect_split_on_device(dev or dcool.dev, block.sig, block.shape, block.row_window, kspec,
@@ -1072,10 +1075,6 @@ def _check_template(kernel):
     pileup, and `kernel.std() > 0` is False for a template with NaN (tests/golden/iterations.npz: borders_error)."""
     if not (np.std(kernel) > 0):
         raise ValueError("Cannot have flat kernel.")
-
-
-def b_is_band(block):
-    return block.sig.layout in (LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED) and not block.inter and getattr(block, "row_window", None) is None
 
 
 def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, workers=4, batch=True, want_windows=True, defer=False,
@@ -1098,7 +1097,7 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
     square = kernel.shape[0] == kernel.shape[1]
     if len(blocks) > 1 and raw and batch and square and tsvd is None:
         live = [k for k, b in enumerate(blocks) if min(b.shape) > max(kernel.shape)]
-        banded = [k for k in live if b_is_band(blocks[k])]
+        banded = [k for k in live if blocks[k].is_band]
         kspec = engine.KernelSpec(kernel, tsvd)
         fin = None
         if len(banded) > 1:
@@ -1126,7 +1125,7 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
     elif len(blocks) > 1 and kernel_config["max_dist"] == 0 and batch and square:
         # 1-D patterns, tables as DataFrames: the same batch, accepted block by block
         live = [k for k, b in enumerate(blocks) if min(b.shape) > max(kernel.shape)]
-        banded = [k for k in live if b_is_band(blocks[k])]
+        banded = [k for k in live if blocks[k].is_band]
         # (on the caller's context and stream: several host threads may be scanning templates side by side)
         res = cid.detect_many_on_device(bdev, [blocks[k] for k in banded], engine.KernelSpec(kernel, tsvd), kernel_config,
                                         raw=raw, want_windows=want_windows, stream=stream) if len(banded) > 1 else None
@@ -1149,7 +1148,7 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
 
     # raw tables of banded intra blocks: the workers only run the native call; the acceptance rules are applied to all
     # their records in one go (numpy under the interpreter lock was a good part of a worker's time on a small block)
-    deferred = raw and square and all(b_is_band(b) and min(b.shape) > max(kernel.shape) for b in blocks)
+    deferred = raw and square and all(b.is_band and min(b.shape) > max(kernel.shape) for b in blocks)
 
     def one(block):
         dev, stream = pool.device()
@@ -1203,8 +1202,7 @@ def detect_inter_block(dcool, ca, cb, kernel_config, kernel, tsvd=None, want_win
     dict that receives strips / tiles / tiles_listed."""
     kernel = np.asarray(kernel, dtype=np.float64)
     budget = _check_budget(inter_budget)
-    s1, e1, s2, e2 = dcool._inter_geometry(ca, cb)
-    n_r, n_c = e1 - s1, e2 - s2
+    n_r, n_c = dcool._inter_geometry(ca, cb)[4:6]
     if min(n_r, n_c) <= max(kernel.shape):
         return None, None
     _check_template(kernel)
@@ -1293,8 +1291,7 @@ def quantify_inter_block(dcool, ca, cb, coords, kernels, kernel_config, tsvd=Non
     budget = _check_budget(inter_budget)
     kernels = [np.asarray(k, dtype=np.float64) for k in kernels]
     km, kn = kernels[0].shape
-    s1, e1, s2, e2 = dcool._inter_geometry(ca, cb)
-    n_r, n_c = e1 - s1, e2 - s2
+    n_r, n_c = dcool._inter_geometry(ca, cb)[4:6]
     coords = np.asarray(coords, dtype=np.int64).reshape(-1, 2)
     n = coords.shape[0]
     out = [(np.full((n, 4), np.nan), np.full((n, km, kn), np.nan)) for _ in kernels]
@@ -1336,7 +1333,7 @@ def detect_blocks_templates(dcool, blocks, kernel_config, kernels, want_windows=
         return None
     if any(k.shape != kernels[0].shape or k.shape[0] != k.shape[1] for k in kernels):
         return None
-    if not all(b_is_band(b) and min(b.shape) > max(kernels[0].shape) for b in blocks):
+    if not all(b.is_band and min(b.shape) > max(kernels[0].shape) for b in blocks):
         return None
     for k in kernels:
         _check_template(k)
@@ -1497,7 +1494,7 @@ def detect(cool, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, 
                 all_windows.append(kernel_windows)
                 kernel = cid.pileup_patterns(kernel_windows)
     if trans:
-        dcool._strip_pool().release()
+        dcool._strips.release()
     if not all_coords:
         empty = pd.DataFrame(columns=OUTPUT_COLUMNS)
         return (empty, np.zeros((0,) + np.shape(kernel_config["kernels"][0]))) if return_windows else empty
@@ -1675,7 +1672,7 @@ def quantify(cool, positions, kernel_config, inter=False, tsvd=None, subsample=N
                 score_out[kernel_id][sel] = table[:, 2]
                 pval_out[kernel_id][sel] = table[:, 3]
                 win_array(kernel_id)[sel] = wins
-        dcool._strip_pool().release()
+        dcool._strips.release()
     if shard is not None:
         win_out = [win_array(k) for k in range(len(kernels))]
         score_out, pval_out, win_out = shard.merge(score_out, pval_out, win_out, [sel for _, _, sel, _ in mine + strips])

@@ -22,7 +22,7 @@ from scipy.sparse import csgraph
 from . import preprocessing as preproc
 from . import stats as cus
 from .. import engine
-from .._lib import (CS_F32, CS_F64, LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED, LAYOUT_DENSE, MASK_BINS, MASK_EXPLICIT, MASK_NONE,
+from .._lib import (CS_F32, CS_F64, LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_DENSE, MASK_BINS, MASK_EXPLICIT, MASK_NONE,
                     FOCUS_DTYPE, CsMatrix, get_device, np_dtype_code)
 
 RESCORE_MARGIN = engine.RESCORE_MARGIN
@@ -764,7 +764,7 @@ def detect_many_on_device(dev, blocks, kspec, kernel_config, *, want_windows=Tru
         kspec = templates[0]
     if kernel_config["max_dist"] != 0 or not blocks or kspec.km != kspec.kn:
         return None
-    if any(b.inter or b.max_dist is None or getattr(b, "row_window", None) is not None for b in blocks):
+    if any(b.inter or b.max_dist is None or b.row_window is not None for b in blocks):
         return None
     missing_tol = kernel_config["max_perc_undetected"] / 100
     if templates is not None:
@@ -835,12 +835,12 @@ def detect_blocks_on_device(dev, blocks, kspec, kernel_config, *, want_windows=T
     beside this call (cs_foci_params.exclusive: one persistent launch for the tiles of all blocks)."""
     if not blocks or kspec.km != kspec.kn or kernel_config["max_dist"] == 0:
         return None
-    if any(b.inter or b.max_dist is None or getattr(b, "row_window", None) is not None or b.sig.layout not in (LAYOUT_BAND, LAYOUT_BAND_LAZY, LAYOUT_BAND_PADDED) for b in blocks):
+    if any(b.max_dist is None or not b.is_band for b in blocks):
         return None
-    if any(b.sig.layout == LAYOUT_BAND_LAZY and getattr(b, "sig32", None) is None for b in blocks):
+    if any(b.sig.layout == LAYOUT_BAND_LAZY and b.sig32 is None for b in blocks):
         return None
     res = engine.run_detect_foci_blocks(
-        dev, [b.sig for b in blocks], [getattr(b, "sig32", None) for b in blocks], [b.shape for b in blocks], kspec,
+        dev, [b.sig for b in blocks], [b.sig32 for b in blocks], [b.shape for b in blocks], kspec,
         pearson=kernel_config["pearson"], lo_diags=[0] * len(blocks), hi_diags=[b.max_dist for b in blocks], inter=False,
         diag_only=False, max_dists=[b.max_dist for b in blocks], miss_rows=[b.miss_row for b in blocks],
         miss_cols=[b.miss_col for b in blocks], missing_tol=kernel_config["max_perc_undetected"] / 100,

@@ -53,8 +53,8 @@ def download_block(dcool, block):
 
 def one_call(blocks):
     """The blocks came from ONE native staging call: they hold the same law buffer (a block of the block-by-block path has none)."""
-    shared = {id(getattr(b, "shared", None)) for b in blocks}
-    return len(shared) == 1 and getattr(blocks[0], "shared", None) is not None
+    shared = {id(b.shared) for b in blocks}
+    return len(shared) == 1 and blocks[0].shared is not None
 
 
 def assert_fit_matters(dcool, chroms, max_dist, largest):

@@ -350,3 +350,79 @@ def test_trans_blocks_equal_the_host_built_block():
             assert np.array_equal(_d2h(dcool.dev, flags.ptr, (e - s,), np.uint8), np.isnan(case.cool["weight"][s:e]).astype(np.uint8))
     check_inputs(case, dcool)
     print(f"trans / stage_inter, stage_inter_many: {len(pairs)} blocks, {n_elem} elements compared, worst error {worst:.2e} relative, excluded: 0")
+
+
+RECORDED = ("cs_csr_band_extent", "cs_csr_median", "cs_csr_median_many", "cs_memcpy_h2d", "cs_memcpy_d2h", "cs_distance_law_csr",
+            "cs_distance_law_finish", "cs_csr_to_band", "cs_stage_blocks", "cs_stage_blocks_opt")
+
+
+def test_staging_routes_issue_their_native_call_sequences(monkeypatch):
+    """Which native entries every staging route calls, in order (plan.StepPlan replays recorded calls, and stage_inter_many
+    exists for its synchronisation count): literal sequences, on `diagonals` at max_dist 60 -- chromosome 0 banded, 1 and 2
+    staged dense.  Then a row strip against those rows of the unsplit trans block, and the width of a view_for view."""
+    case = sc.get("diagonals")
+    dcool = pipeline.DeviceCool(case.cool)
+    md, big = 60, sc.LARGEST
+    assert [pipeline.intra_geometry(case.n(ci), md, big).band for ci in range(3)] == [True, False, False] and dcool.upper
+    log, lib = [], dcool.dev.lib
+
+    def recorder(name, fn):
+        def call(*args):
+            log.append(name[3:])
+            return fn(*args)
+        return call
+
+    for name in RECORDED:
+        monkeypatch.setattr(lib, name, recorder(name, getattr(lib, name)))
+
+    def calls(fn):
+        del log[:]
+        out = fn()
+        return out, list(log)
+
+    extent, median, to_band = "csr_band_extent", "csr_median", "csr_to_band"
+    h2d, d2h = "memcpy_h2d", "memcpy_d2h"
+    ca, cb, rows = 0, 1, (30, 90)
+    whole, seq = calls(lambda: dcool.stage_inter(ca, cb, resident=True))
+    assert seq == [extent, median, h2d, to_band]
+    med, seq = calls(lambda: dcool.inter_median(ca, cb))
+    assert seq == [extent, median] and med > 0
+    _, seq = calls(lambda: dcool.stage_inter(ca, cb, rows=rows, largest_kernel=big, median=None))
+    assert seq == [extent, median, extent, h2d, to_band]
+    strip, seq = calls(lambda: dcool.stage_inter(ca, cb, rows=rows, largest_kernel=big, median=med))
+    assert seq == [extent, h2d, to_band]
+    many, seq = calls(lambda: dcool.stage_inter_many([(0, 1), (0, 2), (1, 2)]))
+    assert seq == [extent] * 3 + ["csr_median_many", h2d] + [to_band] * 3 and len(many) == 3
+    plain = [extent, "distance_law_csr", "distance_law_finish", to_band]
+    fitted = [extent, "distance_law_csr", d2h, d2h, h2d, to_band]
+    for ci in range(3):
+        assert calls(lambda: dcool.stage_intra(ci, md, big))[1] == plain, ci
+        assert case.n(ci) > 2 and calls(lambda: dcool.stage_intra(ci, md, big, smooth=True))[1] == fitted, ci
+    part, seq = calls(lambda: dcool.stage_intra(0, md, big, rows=(50, 120), reduce=lambda x: x))
+    assert seq == fitted and part.row_window == (50, 120)
+    blocks, seq = calls(lambda: dcool.stage_blocks([0, 1, 2], md, big))
+    assert seq == ["stage_blocks"] and all(b.shared is blocks[0].shared is not None for b in blocks)
+    smoothed, seq = calls(lambda: dcool.stage_blocks([0, 1, 2], md, big, smooth=True))
+    assert seq == ["stage_blocks_opt"] and all(b.smooth for b in smoothed) and not any(b.smooth for b in blocks)
+    monkeypatch.undo()
+
+    # a strip staged with the whole block's median holds those rows of the unsplit block, bit for bit, row0 respected
+    n_r, n_c = whole.shape
+    ra, rb = pipeline._strip_rows(n_r, rows, (big - 1) // 2)
+    assert (ra, rb) == (22, 98) and strip.row_window == rows and strip.sig.row0 == ra == strip.view_row0 and strip.inter
+    assert strip.shape == whole.shape and strip.sig.ld == whole.sig.ld == pipeline._inter_ld(n_c) and whole.sig.row0 == 0
+    assert strip.strip_pool is not None and dcool.inter_high_water >= (rb - ra) * strip.sig.ld * 8 and strip.buffer is None
+    got, want = download_rows(dcool, strip.sig, rb - ra), download_rows(dcool, whole.sig, n_r)
+    assert want.any() and np.array_equal(got, want[ra:rb])
+    assert np.array_equal(download_rows(dcool, many[0].sig, n_r), want)
+
+    # a view of a banded block carries the band width the geometry gives for the shorter distance; a dense block has no view
+    geo = pipeline.intra_geometry(case.n(0), 20, big)
+    view = dcool.view_for(blocks[0], 20, big)
+    assert geo.band and view.sig.band_w == geo.in_w == 38 and view.sig32.band_w == geo.in_w and view.keep == geo.keep
+    assert view.sig.ld == blocks[0].sig.ld and view.sig.d_ptr == blocks[0].sig.d_ptr and view.parent is blocks[0] and view.buffer is None
+    assert blocks[0].is_band and view.is_band and not blocks[1].is_band and not whole.is_band and not part.is_band
+    assert dcool.view_for(blocks[1], 20, big) is None and dcool.view_for(smoothed[0], 20, big) is None
+    assert dcool.view_for(blocks[0], md + 1, big) is None
+    print(f"diagonals / call sequences: 9 routes as the parent's, strip of rows {ra}..{rb - 1} of {n_r} x {n_c} bit for bit, "
+          f"view band_w {view.sig.band_w}")
