@@ -265,6 +265,10 @@ _PROTOTYPES = {
                                C.c_void_p]),
     "cs_coarsen": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsCsr), C.POINTER(C.c_int64), C.c_int32, C.c_int32,
                              C.POINTER(CsCsr), C.POINTER(C.c_int64)]),
+    "cs_merge_count": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(CsCsr)), C.c_int32, C.c_void_p, C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_int32)]),
+    "cs_merge_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(CsCsr)), C.c_int32, C.POINTER(CsCsr)]),
+    "cs_merge_tile_columns": (C.c_int32, []),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

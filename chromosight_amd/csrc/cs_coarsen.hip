@@ -25,71 +25,20 @@
 #include <hipcub/hipcub.hpp>
 
 #include "cs_api_internal.h"
+#include "cs_table_rows.h"
 
 using namespace csapi;
 
 namespace {
 
-constexpr int kCoThreads = 256;
 constexpr int kTile = 2048;                 // coarse columns of an LDS tile: 16 KiB of accumulators, 7 workgroups per CU
 constexpr int kRowChunk = kCoThreads;       // fine rows whose ranges are looked up at a time (one per thread)
 constexpr int kWords = kTile / 64;          // ballot words of a tile
-constexpr double kMaxTotal = 9007199254740992.0;        // 2^53
-constexpr int kNoColumn = std::numeric_limits<int>::max();
-
-struct CoStats {
-    unsigned long long bad;                 // bit 0: a count that is not a finite non-negative integer below 2^53; bit 1: a column
-                                            // outside the table or out of order
-    unsigned long long sum_hi, sum_lo;      // the grand total, as the sums of the counts' high and low 32 bits
-    unsigned long long vmax;                // the largest coarse count
-};
-
-// the first position of [lo, hi) whose column is >= key
-__device__ __forceinline__ long long lower_bound(const int* __restrict__ indices, long long lo, long long hi, int key)
-{
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (indices[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // coarse bin of a column (clamped: a column outside the table is reported by the count pass, never used as an index)
 __device__ __forceinline__ int coarse_of(const int* __restrict__ cmap, int n, int col)
 {
     return cmap[min(max(col, 0), n - 1)];
-}
-
-// the statistics of a workgroup's threads into *out (s_red: 4 words per wave of LDS that nobody else is using)
-__device__ __forceinline__ void block_stats(unsigned long long bad, unsigned long long sum_hi, unsigned long long sum_lo,
-                                            unsigned long long vmax, unsigned long long* s_red, CoStats* __restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        bad |= __shfl_down(bad, d);
-        sum_hi += __shfl_down(sum_hi, d);
-        sum_lo += __shfl_down(sum_lo, d);
-        vmax = max(vmax, __shfl_down(vmax, d));
-    }
-    if (lane == 0) {
-        s_red[4 * wave] = bad;
-        s_red[4 * wave + 1] = sum_hi;
-        s_red[4 * wave + 2] = sum_lo;
-        s_red[4 * wave + 3] = vmax;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CoStats t = {0, 0, 0, 0};
-        for (int w = 0; w < kCoThreads / 64; ++w) {
-            t.bad |= s_red[4 * w];
-            t.sum_hi += s_red[4 * w + 1];
-            t.sum_lo += s_red[4 * w + 2];
-            t.vmax = max(t.vmax, s_red[4 * w + 3]);
-        }
-        *out = t;
-    }
 }
 
 template <typename TV, typename TO, bool WRITE>
@@ -107,7 +56,7 @@ __global__ __launch_bounds__(kCoThreads) void co_rows_kernel(const long long* __
     __shared__ int s_pre[kRowChunk + 1];
     __shared__ int s_wpre[kWords];
     __shared__ int s_next, s_maxc, s_total;
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     unsigned long long bad = 0, sum_hi = 0, sum_lo = 0, vmax = 0;
 
     for (int R = blockIdx.x; R < n_coarse; R += gridDim.x) {
@@ -198,39 +147,9 @@ __global__ __launch_bounds__(kCoThreads) void co_rows_kernel(const long long* __
                 __syncthreads();
             }
             const int next = s_next;
-            // the nonzero accumulators, in column order
-            const int nw = (span + 63) >> 6;
-            for (int c = tid; c < nw * 64; c += kCoThreads) {
-                const unsigned long long a = c < span ? s_acc[c] : 0ull;
-                const unsigned long long mask = __ballot(a != 0);
-                if (lane == 0) s_words[c >> 6] = mask;
-            }
-            __syncthreads();
-            if (tid < 64) {
-                const int x = tid < nw ? __popcll(s_words[tid]) : 0;
-                int inc = x;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int y = __shfl_up(inc, d);
-                    if (lane >= d) inc += y;
-                }
-                if (tid < kWords) s_wpre[tid] = inc - x;
-                if (tid == 63) s_total = inc;
-            }
-            __syncthreads();
-            for (int c = tid; c < span; c += kCoThreads) {
-                const unsigned long long a = s_acc[c];
-                if (!a) continue;
-                if (WRITE) {
-                    const int w = c >> 6;
-                    const long long at = row_out + written + s_wpre[w] + __popcll(s_words[w] & ((1ull << lane) - 1ull));
-                    out_indices[at] = base + c;
-                    out_data[at] = (TO)a;
-                } else {
-                    vmax = max(vmax, a);
-                }
-            }
-            written += s_total;
+            // the nonzero accumulators, in column order (the output has room for every input pixel)
+            written += emit_tile<kTile, TO, WRITE>(s_acc, s_words, s_wpre, &s_total, span, base, row_out + written, kNoLimit,
+                                                   out_indices, out_data, vmax);
             if (next < top) bad |= 2;                      // a row that is not sorted by column
             base = max(next, top);
         }
@@ -241,39 +160,6 @@ __global__ __launch_bounds__(kCoThreads) void co_rows_kernel(const long long* __
         block_stats(bad, sum_hi, sum_lo, vmax, s_acc, &stats[blockIdx.x]);
     }
 }
-
-// the workgroups' statistics (parts[0 .. n_parts)) into parts[n_parts]; one workgroup
-__global__ __launch_bounds__(kCoThreads) void co_stats_kernel(CoStats* __restrict__ parts, int n_parts)
-{
-    __shared__ unsigned long long s_red[4 * (kCoThreads / 64)];
-    unsigned long long bad = 0, sum_hi = 0, sum_lo = 0, vmax = 0;
-    for (int i = threadIdx.x; i < n_parts; i += kCoThreads) {
-        const CoStats p = parts[i];
-        bad |= p.bad;
-        sum_hi += p.sum_hi;
-        sum_lo += p.sum_lo;
-        vmax = max(vmax, p.vmax);
-    }
-    block_stats(bad, sum_hi, sum_lo, vmax, s_red, &parts[n_parts]);
-}
-
-// device allocations of one call, freed on every way out (hipFree waits for the work that uses them)
-struct CallBuffers {
-    std::vector<void*> p;
-    ~CallBuffers()
-    {
-        for (void* q : p) (void)hipFree(q);
-    }
-    template <typename T>
-    hipError_t get(T** out, size_t count)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(count * sizeof(T), 1));
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-};
 
 template <typename TV, typename TO, bool WRITE>
 void launch_rows(int grid, hipStream_t stream, const cs_csr* g, const int* cmap, const int* cfirst, int n_coarse, long long* row_count,

@@ -444,14 +444,15 @@ class DeviceCool:
 
     @classmethod
     def from_device_csr(cls, parent, indptr, indices, data, nnz, val_dtype, *, offsets=_PARENT, binsize=_PARENT, bin_start=_PARENT,
-                        bin_end=_PARENT, weight=_PARENT):
+                        bin_end=_PARENT, weight=_PARENT, upper=_PARENT):
         """A DeviceCool over a pixel table already in HBM (device buffers of the CSR: n_bins + 1 row pointers, column bins and
         counts, the first `nnz` entries used -- the result of subsample.subsample_csr), with `parent`'s bins, names and weights.
         The counts are non-negative integers: val_dtype is float32 when they are all below 2^24, as the constructor would
         choose for an upload of the same table.  `.host` is downloaded once, when first read.
         offsets, binsize, bin_start, bin_end, weight: geometry and weights that differ from the parent's (a table of other bins:
         coarsen.coarsen_csr); weight=None makes a table without weights.  The chromosomes and their names stay the parent's, and a
-        table whose pixels are the parent's regrouped by a monotone map of the bins is upper-triangle when the parent is."""
+        table whose pixels are the parent's regrouped by a monotone map of the bins is upper-triangle when the parent is.
+        upper: whether every pixel lies on or above the diagonal, for a caller that knows (merge.merge_device: all sources do)."""
         self = cls.__new__(cls)
         self.dev = parent.dev
         self.offsets = parent.offsets if offsets is _PARENT else np.asarray(offsets, dtype=np.int64)
@@ -469,7 +470,10 @@ class DeviceCool:
         weight = parent.host_weight if weight is _PARENT else weight
         self._host, self._host_weight = None, weight
         # a subset of an upper-triangle table is one; anything else is checked on the pixels
-        self.upper = True if parent.upper else bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]))
+        if upper is not _PARENT:
+            self.upper = bool(upper)
+        else:
+            self.upper = True if parent.upper else bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]))
         self._init_resident(weight)
         return self
 
@@ -1032,6 +1036,18 @@ class DeviceCool:
         from .coarsen import coarsen_device
         return coarsen_device(self, factor)
 
+    def merged(self, *others):
+        """A DeviceCool over the pixel-wise sum of this table and `others` (DeviceCools over the same bins, resident on the same
+        device), built on the device (chromosight_amd/merge.py, cs_merge_count / cs_merge_fill): what `cooler merge` writes --
+        one pixel for every (bin1, bin2) stored in at least one source, the counts summed, nothing mirrored.  A pixel whose
+        summed count is 0 is not stored.  The counts must be non-negative integers (ValueError otherwise, as for sources over
+        different bins or devices, and for more than 64 of them).  The sum is exact, so the table is bitwise the same for every
+        order of the sources, on every run and device.  The sources stay valid and untouched; the result has no weights (the sum
+        of balanced tables is not balanced): balance it (balance.ice_balance + set_weights, or pipeline.open_cool([...])).
+        Without `others` the result is a table equal to this one, with its weights."""
+        from .merge import merge_device
+        return merge_device([self, *others])
+
     def bins_of(self, chroms, positions):
         """Whole-genome bin of (chromosome name, base pair) pairs; -1 outside the genome
         (HicGenome.coords_to_bins, contacts_map.py:404-450, for fixed-size bins)."""
@@ -1373,29 +1389,56 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
     min_nnz=10, max_iters=200; chromosight_amd/balance.py).  Unlike the reference, the new weights are NOT written back
     into the input file.  The result goes to detect / quantify / detect_to_files and the parallel drivers.
 
+    A list or tuple of them (replicates over the same bins): each is read and uploaded, and all are merged on the device
+    (DeviceCool.merged: what `cooler merge` writes, which the reference expects to have been run beforehand).  The sum of
+    balanced tables is not balanced, so the merged table counts as a file without stored weights: ICE on it for "auto" and
+    "force", its detectable bins with weights 1.0 / NaN for "raw".  The sources are released once merged; the peak in HBM is
+    sources + result.  A list of one behaves exactly as its element alone.  The merge is exact, so every rank of a parallel run
+    that merges its own copies gets the same table and the same weights.
+
     resolution: None, or the bin size in base pairs to work at, a positive multiple of the file's (ValueError otherwise).  A
-    larger one coarsens the uploaded table on the device (DeviceCool.coarsened: what `cooler coarsen` writes, which the reference
-    expects to have been run beforehand); the coarse table has no stored weights, so `norm` applies as to a file without any:
-    ICE on the coarse table for "auto" and "force", its detectable bins with weights 1.0 / NaN for "raw".  The file's own bin
-    size: as without the argument.  Every rank of a parallel run that coarsens its own copy gets the same table and weights."""
+    larger one coarsens the uploaded (and, for a list, merged) table on the device (DeviceCool.coarsened: what `cooler coarsen`
+    writes, which the reference expects to have been run beforehand); the coarse table has no stored weights, so `norm` applies as
+    to a file without any: ICE on the coarse table for "auto" and "force", its detectable bins with weights 1.0 / NaN for "raw".
+    The file's own bin size: as without the argument.  Every rank of a parallel run that coarsens its own copy gets the same table
+    and weights."""
     if norm not in ("auto", "raw", "force"):
         raise ValueError("norm must be one of: auto, raw, force")
-    if isinstance(uri_or_cool, (str, bytes)) or hasattr(uri_or_cool, "__fspath__"):
-        from . import io as cio
-        cool = cio._read_cool(uri_or_cool, balance)
+
+    def read(source):
+        if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+            from . import io as cio
+            return cio._read_cool(source, balance)
+        return dict(source)
+
+    if isinstance(uri_or_cool, (list, tuple)):
+        if not uri_or_cool:
+            raise ValueError("open_cool got an empty list: at least one .cool is needed")
+        cools = [read(source) for source in uri_or_cool]
     else:
-        cool = dict(uri_or_cool)
+        cools = [read(uri_or_cool)]
+    cool = cools[0]
     factor = 1
     if resolution is not None:
         binsize = int(cool["binsize"])
         if isinstance(resolution, bool) or int(resolution) != resolution or resolution <= 0 or int(resolution) % binsize:
             raise ValueError(f"resolution {resolution} is not a positive multiple of the file's bin size {binsize}")
         factor = int(resolution) // binsize
-    # a coarsened table has no stored weights: the fine bins' mean nothing for the coarse ones
-    weight = None if norm == "force" or factor > 1 else cool.get("weight")
+    # a coarsened table has no stored weights (the fine bins' mean nothing for the coarse ones), nor has a merged one
+    weight = None if norm == "force" or factor > 1 or len(cools) > 1 else cool.get("weight")
     raw = (lambda w: np.where(np.isfinite(np.asarray(w, dtype=np.float64)), 1.0, np.nan)) if norm == "raw" else (lambda w: w)
-    cool["weight"] = None if weight is None else raw(weight)
-    dcool = DeviceCool(cool, dev)
+    if len(cools) > 1:
+        parts = []
+        while cools:
+            part = cools.pop(0)
+            part["weight"] = None
+            parts.append(DeviceCool(part, dev))
+        del part, cool
+        dcool = parts[0].merged(*parts[1:])
+        del parts                                   # the sources' HBM is released here
+    else:
+        cool["weight"] = None if weight is None else raw(weight)
+        dcool = DeviceCool(cool, dev)
     if factor > 1:
         dcool = dcool.coarsened(factor)
     if weight is None:

@@ -426,6 +426,28 @@ int cs_subsample(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t*
 int cs_coarsen(cs_ctx* ctx, void* stream, const cs_csr* genome, const int64_t* chrom_offsets, int32_t n_chrom, int32_t factor,
                cs_csr* out, int64_t* h_out_nnz);
 
+/* ---- merging of resident pixel tables over the same bins: what `cooler merge` writes (pooling replicates, which the reference
+ * leaves to cooler, before chromosight is started) ----
+ * tables: n_tables (1 .. 64; 0: CS_ERR_INVALID, more: CS_ERR_UNSUPPORTED) resident pixel tables, each as cs_coarsen takes them
+ * (square, plain row pointers, no weights, nnz < 2^31 - 1, columns sorted within every row; anything else: CS_ERR_INVALID), all of
+ * the same n_rows.  The merged table holds one pixel for every (bin1, bin2) stored in at least one table, its count the sum of the
+ * tables' counts there, rows sorted by column; a pixel whose sum is 0 is not stored; nothing is mirrored.  Counts must be finite
+ * non-negative integers (CS_F32 and CS_F64 tables mix freely) with a grand total over all tables below 2^53 (anything else:
+ * CS_ERR_INVALID), so every sum is exact: the result is bitwise the same for any order of the tables, launch shape, context or
+ * device (integer LDS atomics only, no float atomics).  A merged table of 2^31 - 1 pixels or more: CS_ERR_UNSUPPORTED.
+ * The size of the result is not bounded usefully by an input, so the call is split and the caller allocates at the exact size:
+ * cs_merge_count validates the tables, writes the n_rows + 1 row pointers to d_out_indptr and reports the number of pixels and the
+ *   dtype of the counts (CS_F32 when every sum is below 2^24, else CS_F64).  All tables empty: zero row pointers, 0 pixels, no launch.
+ * cs_merge_fill takes `out` with n_rows = n_cols = the tables', d_indptr as cs_merge_count wrote it, nnz and dtype as it reported
+ *   them and d_indices / d_data of exactly nnz entries of that dtype (row pointers that do not end at out->nnz: CS_ERR_INVALID),
+ *   and writes the pixels sorted by (bin1, bin2).  No store goes beyond out->nnz entries.
+ * cs_merge_tile_columns: the columns of a row that one pass through on-chip memory covers (tests and documents).
+ * Both calls are synchronous; the tables are never written. */
+int cs_merge_count(cs_ctx* ctx, void* stream, const cs_csr* const* tables, int32_t n_tables, int64_t* d_out_indptr, int64_t* h_out_nnz,
+                   int32_t* h_out_dtype);
+int cs_merge_fill(cs_ctx* ctx, void* stream, const cs_csr* const* tables, int32_t n_tables, cs_csr* out);
+int32_t cs_merge_tile_columns(void);
+
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
     double pearson;         /* candidate threshold: coefficient >= pearson and != 0 (detection.py:417-421) */
