@@ -468,7 +468,7 @@ DispatchSwitches read_dispatch_switches()
         {"WIDE_ALL", &sw.wide_all, nullptr}, {"NO_LARGE", &sw.no_large, nullptr}, {"NO_SEPARABLE", &sw.no_separable, nullptr},
         {"SEPARABLE_FIRST", &sw.separable_first, nullptr}, {"NO_REGULAR_MASK", &sw.no_regular_mask, nullptr},
         {"FULL_MASK_TABLES", &sw.full_mask_tables, nullptr}, {"MFMA_NORSYM", &sw.mfma_norsym, nullptr},
-        {"NO_SYMMETRY", &sw.no_symmetry, nullptr}, {"DEBUG", &sw.debug, nullptr}, {"MFMA", nullptr, &sw.mfma},
+        {"NO_SYMMETRY", &sw.no_symmetry, nullptr}, {"DEBUG", &sw.debug, nullptr}, {"MFMA_WAVES4", &sw.mfma_waves4, nullptr}, {"MFMA", nullptr, &sw.mfma},
         {"MFMA_REG", nullptr, &sw.mfma_reg}, {"LARGE", nullptr, &sw.large}, {"LOWRANK", nullptr, &sw.lowrank},
     };
     constexpr size_t kPrefix = sizeof("CHROMOSIGHT_HIP_") - 1;
@@ -833,13 +833,14 @@ static int run_lowrank(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
 }
 
 // the tile kernels of cs_corr_mfma.hip: weight image, launch, and which instance ran
-static int launch_tile_kernel(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+static int launch_tile_kernel(cs_ctx* ctx, cs::CorrArgs<float>& A, const DispatchSwitches& sw, hipStream_t stream)
 {
     cs::MfmaWeights E;
+    ctx->last_dense_waves = 0;
     int rc = ensure_wfrag(ctx, stream, A.km, A.kn, &E);
     if (rc != CS_OK) return rc;
     int path = 0;
-    rc = cs::launch_corr_mfma_f32(A, E, stream, &path);
+    rc = cs::launch_corr_mfma_f32(A, E, stream, &path, sw.mfma_waves4, &ctx->last_dense_waves);
     ctx->last_kernel = path == 1 ? CS_KERNEL_MFMA_DENSE : path == 2 ? CS_KERNEL_MFMA_REG : path == 3 ? CS_KERNEL_MFMA_LIST : CS_KERNEL_MFMA;
     return rc;
 }
@@ -861,7 +862,7 @@ static int run_mfma_reg(cs_ctx* ctx, cs::CorrArgs<float>& A, const DispatchSwitc
         rc = narrow_f64_rows(ctx, A, A.sig.layout == CS_LAYOUT_BAND ? A.sig.band_w : A.ns, stream);
         if (rc != CS_OK) return rc;
     }
-    rc = sink_result(ctx, launch_tile_kernel(ctx, A, stream));
+    rc = sink_result(ctx, launch_tile_kernel(ctx, A, sw, stream));
     if (rc == CS_OK && (ctx->last_kernel == CS_KERNEL_MFMA_REG || ctx->last_kernel == CS_KERNEL_MFMA_LIST) && A.cand_keys) ctx->cand_fused = true;
     return rc;
 }
@@ -895,13 +896,13 @@ static int run_mfma_large(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t strea
 }
 
 // the dense and the general instance of the tile kernel
-static int run_mfma(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
+static int run_mfma(cs_ctx* ctx, cs::CorrArgs<float>& A, const DispatchSwitches& sw, hipStream_t stream)
 {
     if (A.sig_is_f64 && A.mask_mode == 0 && A.sig.layout == 0 && A.out.layout == 0 && !A.nobs.ptr) {
         const int rc = narrow_f64_rows(ctx, A, A.ns, stream);      // so that the persistent tile kernel can stage them
         if (rc != CS_OK) return rc;
     }
-    return map_result(ctx, A.km, A.kn, launch_tile_kernel(ctx, A, stream));
+    return map_result(ctx, A.km, A.kn, launch_tile_kernel(ctx, A, sw, stream));
 }
 
 template <typename TC>
@@ -959,7 +960,7 @@ int launch_corr<float>(cs_ctx* ctx, cs::CorrArgs<float>& A, hipStream_t stream)
     if (fast && !A.out.ptr && mfma_wide_wanted(A, sw) && !A.w_rank1) return run_mfma_wide(ctx, A, stream);
     if (fast && mfma_large_wanted(A, sw)) return run_mfma_large(ctx, A, stream);
     if (!A.out.ptr) return CS_NEED_MAP;      // every other kernel writes a map
-    if (fast && mfma_wanted(A, sw)) return run_mfma(ctx, A, stream);
+    if (fast && mfma_wanted(A, sw)) return run_mfma(ctx, A, sw, stream);
     if (fast && stream_wanted(A, sw)) return run_stream(ctx, A, sw, stream);
     if (fast && separable_wanted(A, sw)) return run_separable(ctx, A, stream);
     if (fast && mfma_wide_wanted(A, sw)) return run_mfma_wide(ctx, A, stream);
@@ -1250,6 +1251,7 @@ extern "C" {
 const char* cs_version(void) { return "chromosight_hip 0.1 (gfx950)"; }
 
 int cs_last_kernel(const cs_ctx* ctx) { return ctx ? ctx->last_kernel : 0; }
+int cs_last_dense_waves(const cs_ctx* ctx) { return ctx && ctx->last_kernel == CS_KERNEL_MFMA_DENSE ? ctx->last_dense_waves : 0; }
 
 int cs_ctx_set_range_check(cs_ctx* ctx, int32_t on)
 {

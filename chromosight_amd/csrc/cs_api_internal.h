@@ -127,6 +127,7 @@ struct cs_ctx {
     std::vector<char> stage_uploaded;   // cs_stage_blocks: the tables the staging scratch holds (skip the upload of identical ones)
     void* d_rim = nullptr;          // rim tables of the mask weight sets (cs_launch.h MfmaWeights::rim), same key as wfrag
     int last_kernel = 0;     // cs_last_kernel()
+    int last_dense_waves = 0;        // cs_last_dense_waves(): waves per workgroup of the dense tile kernel (CS_KERNEL_MFMA_DENSE)
     int range_check = 0;     // cs_ctx_set_range_check()
     bool cand_fused = false; // the last candidate-mode call appended its candidates itself (no map was written)
     long long cand_hint = 0, cand_hint_pixels = 0;   // cs_detect_foci_blocks: candidates, pixels and blocks of the previous call
@@ -350,7 +351,7 @@ int launch_corr<double>(cs_ctx* ctx, cs::CorrArgs<double>& A, hipStream_t stream
 // that starts with that digit and -1 otherwise (unset: the measured default).
 struct DispatchSwitches {
     bool force_generic, no_mfma, no_wide, wide_all, no_large, no_separable, separable_first, no_regular_mask, full_mask_tables,
-        mfma_norsym, no_symmetry, debug;
+        mfma_norsym, no_symmetry, debug, mfma_waves4;
     int mfma, mfma_reg, large, lowrank;
 };
 DispatchSwitches read_dispatch_switches();

@@ -77,8 +77,18 @@ __device__ unsigned long long cs_mf_prof[16];
         tprev_ = now_;                                                     \
     } while (0)
 #define MF_PROF_ADD(k, v) atomicAdd(&cs_mf_prof[k], (unsigned long long)(v))
+// Wall clock of the persistent kernels' workgroups (the constant 100 MHz counter, not the shader clock): prologue, tile loop and what
+// follows it in slots 12, 13, 14 of prof_lds, the number of workgroups in slot 5.  Cycles of the loop's phases over the loop's
+// wall time is the clock the kernel ran at.
+#define MF_WALL(k)                                                           \
+    do {                                                                     \
+        const unsigned long long w_ = __builtin_amdgcn_s_memrealtime();      \
+        if (tid == 0) prof_lds[k] += w_ - wall_;                             \
+        wall_ = w_;                                                          \
+    } while (0)
 #else
 #define MF_STAMP(k)
+#define MF_WALL(k)
 #endif
 
 __device__ __forceinline__ f4 mfma16(const h8& a, const h8& b, const f4& c)
@@ -755,6 +765,9 @@ __global__ __launch_bounds__(256, 2) void corr_mfma_blocks_kernel(const MfmaBloc
     }
 }
 
+// the headline configuration at four waves per SIMD: corr_mfma_dense8_kernel
+#include "cs_corr_mfma_dense8.inc"
+
 // The 160 KB dynamic-LDS ceiling is a per-function, per-device attribute: set it the first time a kernel is
 // launched on a device (the call costs microseconds on every launch otherwise).
 static hipError_t allow_big_lds(const void* fn)
@@ -801,9 +814,10 @@ static int dense_tile_skew(int tiles_x, long long n_tiles, int step)
     return best;
 }
 
-int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t stream, int* dense_path)
+int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t stream, int* dense_path, bool waves4, int* dense_waves)
 {
     *dense_path = 0;
+    if (dense_waves) *dense_waves = 0;
     A.tile_w = A.tile_h = MF_T;
     A.tiles_y = (A.row_end - A.row_begin + MF_T - 1) / MF_T;
     if (A.out.layout == 1) {
@@ -974,12 +988,22 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
         // (checked bit for bit against 4-byte transfers at every misalignment), the 16-byte stores aligned rows
         const bool vec4 = ((uintptr_t)D.out % 32 == 0) && D.ld_out % 4 == 0 &&
                           ((A.kn - 1) / 2) % 4 == 0 && D.ns % 4 == 0 && D.ns >= 4 && !getenv("CHROMOSIGHT_HIP_MFMA_NOVEC");
-        const void* kd = vec4 ? (const void*)corr_mfma_dense_kernel<true, false> : (const void*)corr_mfma_dense_kernel<false, false>;
+        // The headline configuration -- 16-byte transfers, a 17 x 17 template whose rows mirror -- runs the same tile with eight
+        // waves of at most 128 registers, four per SIMD (cs_corr_mfma_dense8.inc); CHROMOSIGHT_HIP_MFMA_WAVES4 keeps the 4-wave
+        // instance, which serves every other dense call.
+        const bool waves8 = vec4 && A.mfma_rsym != 0 && A.km == 17 && A.kn == 17 && !waves4;
+        const void* kd = waves8 ? (const void*)corr_mfma_dense8_kernel
+                         : vec4 ? (const void*)corr_mfma_dense_kernel<true, false> : (const void*)corr_mfma_dense_kernel<false, false>;
         hipError_t e2 = allow_big_lds(kd);
         if (e2 != hipSuccess) return (int)e2;
         const int per_cu = 2;
         const int grid = (int)std::min<long long>(blocks, (long long)per_cu * A.n_cu);
         D.xcd_order |= dense_tile_skew(A.tiles_x, blocks, (D.xcd_order & 1) && grid % 8 == 0 ? grid / 8 : grid) << 1;
+        if (dense_waves) *dense_waves = waves8 ? 8 : 4;
+        if (waves8) {
+            hipLaunchKernelGGL(corr_mfma_dense8_kernel, dim3((unsigned)grid), dim3(512), MF8_LAUNCH, stream, D);
+            return (int)hipGetLastError();
+        }
         if (vec4) hipLaunchKernelGGL((corr_mfma_dense_kernel<true, false>), dim3((unsigned)grid), dim3(256), (MFD_LAUNCH_EXTRA ? MFD_SMEM_REG + MFD_LAUNCH_EXTRA : MFD_SMEM), stream, D);
         else hipLaunchKernelGGL((corr_mfma_dense_kernel<false, false>), dim3((unsigned)grid), dim3(256), (MFD_LAUNCH_EXTRA ? MFD_SMEM_REG + MFD_LAUNCH_EXTRA : MFD_SMEM), stream, D);
         return (int)hipGetLastError();

@@ -24,9 +24,11 @@
 #define MF_PROF_ADD(k, v) (prof_lds[k] += (unsigned long long)(v))
     unsigned long long* const prof_lds = reinterpret_cast<unsigned long long*>(smem + MFD_PROF);
     unsigned long long tprev_ = 0;
+    unsigned long long wall_ = __builtin_amdgcn_s_memrealtime();
     if (tid == 0)
         for (int k = 0; k < 16; ++k) prof_lds[k] = 0;
     auto prof_flush = [&]() {
+        if (tid == 0) prof_lds[5] += 1ull;
         if (tid == 0)
             for (int k = 0; k < 16; ++k)
                 if (prof_lds[k]) atomicAdd(&cs_mf_prof[k], prof_lds[k]);
@@ -840,6 +842,7 @@
     }
     // REG: one emit site (its epilogue is 4 K instructions) -- the loop runs one pass beyond the last tile, in which
     // only the pending tile is emitted.  The dense instances emit the last tile after the loop.
+    MF_WALL(12);
     for (;; tile += tile_step) {
         const bool have = REG ? tile < tile_end : true;              // uniform over the workgroup
         if constexpr (REG) {
@@ -1235,9 +1238,11 @@
         slot ^= 1;
         pending = true;
     }
+    MF_WALL(13);
     if constexpr (!REG) {
         if (pending) emit(p_I0, p_J0, p_unscale, p_acc, p_S1, p_S2, p_hdr, p_slot);
     }
+    MF_WALL(14);
 #ifdef CS_MF_PROFILE
     prof_flush();
 #undef MF_PROF_ADD

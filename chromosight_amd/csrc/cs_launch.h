@@ -55,7 +55,9 @@ struct MfmaWeights {
 };
 constexpr int kRimPW = 0, kRimQW = 2 * 17 * 18, kRimW = 4 * 17 * 18, kRimBase = 4 * 17 * 18 + 2 * 289;
 constexpr int kRimFloats = kRimBase + 3 * 17;
-int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s, int* dense_path);
+// waves4: the dense 17 x 17 mirrored-row call keeps the 4-wave instance; dense_waves: 8 or 4 waves per workgroup of the dense tile
+// kernel that ran, 0 when another kernel served the call
+int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s, int* dense_path, bool waves4 = false, int* dense_waves = nullptr);
 // Several matrices in one persistent launch of the masked candidate instance (corr_mfma_blocks_kernel).  h_table: page-locked,
 // mfma_blocks_table_bytes(n) bytes, argument block b (CorrArgs::defer_args of launch_corr_mfma_f32) at
 // h_table + mfma_blocks_arg_offset(n) + b * mfma_blocks_arg_bytes(); d_table: as many device bytes.  The table is

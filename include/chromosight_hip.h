@@ -95,6 +95,10 @@ enum { CS_KERNEL_NONE = 0, CS_KERNEL_GENERIC = 1, CS_KERNEL_STREAM = 2, CS_KERNE
        CS_KERNEL_MFMA_REG = 5, CS_KERNEL_SEPARABLE = 6, CS_KERNEL_MFMA_WIDE = 7, CS_KERNEL_MFMA_LIST = 8,
        CS_KERNEL_MFMA_LARGE = 9, CS_KERNEL_LOWRANK = 10 };
 int cs_last_kernel(const cs_ctx* ctx);
+/* CS_KERNEL_MFMA_DENSE comes in two instances of the same kernel: 8 waves per workgroup (16-byte transfers and a 17 x 17 template
+ * whose rows mirror; four waves per SIMD) and 4 waves (every other dense call, or CHROMOSIGHT_HIP_MFMA_WAVES4=1).  Returns 8 or 4,
+ * or 0 when the dense tile kernel did not serve the last call. */
+int cs_last_dense_waves(const cs_ctx* ctx);
 /* Range guard of the device entries (off by default).  The reference sums every window on its own
  * (detection.py:1002-1018) and zeroes exactly the windows that hold a non-finite pixel (:1088-1101); the device kernels
  * keep running box sums and square in float32, so a DEVICE-RESIDENT map handed to cs_normxcorr2 must be finite and, for

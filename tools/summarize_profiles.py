@@ -55,7 +55,8 @@ def per_dispatch(path, kernel_substr):
     return {k: sum(v) / len(v) for k, v in acc.items()}
 
 
-CORR_KERNELS = ("corr_stream_kernel", "corr_mfma_dense_kernel")      # the dominant kernel of a correlation call
+CORR_KERNELS = ("corr_stream_kernel", "corr_mfma_dense_kernel", "corr_mfma_dense8_kernel")      # the dominant kernel of a correlation call
+# (corr_mfma_dense8_kernel: the 8-wave instance that serves C2 -- cs_corr_mfma_dense8.inc)
 
 
 summary = {"note": "per-dispatch means from rocprofv3 --pmc passes (one counter group per pass) on "
@@ -78,7 +79,7 @@ for w, key in (("c2", "c2_4096_f32"), ("c3k", "c3k_band_50000x234"), ("c4p", "c4
         if rec.get("SQ_VALU_MFMA_BUSY_CYCLES") and rec.get("GRBM_GUI_ACTIVE"):
             # busy cycles are summed over the 1024 SIMDs, GUI_ACTIVE over the 8 XCDs
             rec["mfma_pipe_busy_frac"] = (rec["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024.0) / (rec["GRBM_GUI_ACTIVE"] / 8.0)
-    rec["kernel"] = "corr_mfma_dense_kernel (<VEC4, REG, RSYM> instance: see the kernel trace)"
+    rec["kernel"] = "corr_mfma_dense_kernel (<VEC4, REG, RSYM> instance) or corr_mfma_dense8_kernel (C2): see the kernel trace"
     if "FETCH_SIZE" in rec and "WRITE_SIZE" in rec:
         rec["hbm_bytes_per_dispatch"] = (rec["FETCH_SIZE"] * f + rec["WRITE_SIZE"]) * 1024.0
         rec["hbm_bytes_note"] = (f"FETCH_SIZE x {f:.3f} (calibration) + WRITE_SIZE, KiB -> bytes")
