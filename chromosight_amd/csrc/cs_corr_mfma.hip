@@ -1088,3 +1088,16 @@ int launch_corr_mfma_blocks(void* h_table, void* d_table, int n_blocks, int rsym
 }
 
 }  // namespace cs
+
+// The (I0, J0) sequence of workgroup `block` of the 8-wave dense instance, by the walk the kernel itself uses (DenseTileWalk):
+// what a host test compares with the division form.  Fills at most `cap` entries, returns the number of tiles of the workgroup.
+extern "C" int cs_dense_tile_walk(int tiles_x, int n_tiles, int grid, int xcd_order, int row_begin, int block, int* i0, int* j0, int cap)
+{
+    if (tiles_x <= 0 || n_tiles < 0 || grid <= 0 || block < 0 || block >= grid) return -1;
+    cs::DenseTileWalk walk;
+    walk.init(tiles_x, n_tiles, grid, xcd_order, block);
+    int n = 0;
+    for (; !walk.done(); walk.advance(), ++n)
+        if (n < cap) walk.origin(row_begin, i0[n], j0[n]);
+    return n;
+}

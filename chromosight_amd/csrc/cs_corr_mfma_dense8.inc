@@ -10,6 +10,10 @@
 // the kernel fits 128 registers: two workgroups per CU are four waves per SIMD.  Every pixel sees the operations of the
 // 4-wave instance in the same order; the one decision taken per WAVE -- the lean or the literal form of the coefficient -- now
 // covers 16 x 32 pixels instead of 16 x 64.
+//
+// Twice the waves repeat what a wave does per tile beside its MFMAs, so that part is kept short (DESIGN.md "The 8-wave dense
+// kernel: what each wave repeats per tile"): the tile walk is carried without divisions (DenseTileWalk), no staging lane is
+// masked, the wave maximum runs on bit patterns (wave_max_bits).  None of it changes a value.
 
 constexpr int MF8_ROWS_PER_THREAD = 7;          // staging: 480 threads = 40 column pairs x 12 row groups
 constexpr int MF8_RED = MFD_WL + 18 * 1024;     // four planes, 9 tail + 9 head rows of weights, then the 8 wave maxima
@@ -21,6 +25,74 @@ constexpr int MF8_LAUNCH = MF8_SMEM + 128;
 constexpr int MF8_LAUNCH = MF8_SMEM;
 #endif
 static_assert(MF8_LAUNCH <= 80 * 1024, "two workgroups per CU");
+
+// The tile sequence of one workgroup, carried from tile to tile without a division.  The order is that of the 4-wave instance
+// (cs_corr_mfma_body.inc): XCD x takes the tiles [x n / 8, (x + 1) n / 8) of the row-major list and its workgroups walk that
+// range side by side, `step` tiles at a time; tile row `by` is skewed by (by * skew) % tiles_x columns (dense_tile_skew).  The
+// step is constant per workgroup, so its quotient and remainder by tiles_x, and what they add to the skew, are formed once.
+struct DenseTileWalk {
+    int tile, tile_end, step;        // position in the row-major tile list, end of the workgroup's range, tiles per step
+    int by, bx, sk;                  // tile row, tile column before the skew, (by * skew) % tiles_x
+    int tiles_x, d_by, d_bx;         // step = d_by * tiles_x + d_bx
+    int d_sk, sk_carry;              // (d_by * skew) % tiles_x; skew % tiles_x: one more tile row when bx wraps
+
+    __host__ __device__ void init(int tiles_x_, int n_tiles, int grid, int xcd_order, int block)
+    {
+        tiles_x = tiles_x_;
+        if ((xcd_order & 1) && grid % 8 == 0) {
+            const int x = block & 7, per = (n_tiles + 7) / 8;
+            tile = x * per + (block >> 3);
+            tile_end = (x + 1) * per < n_tiles ? (x + 1) * per : n_tiles;
+            step = grid >> 3;
+        } else {
+            tile = block;
+            tile_end = n_tiles;
+            step = grid;
+        }
+        const int skew = xcd_order >> 1;
+        by = tile / tiles_x;
+        bx = tile - by * tiles_x;
+        sk = (by * skew) % tiles_x;
+        d_by = step / tiles_x;
+        d_bx = step - d_by * tiles_x;
+        d_sk = (d_by * skew) % tiles_x;
+        sk_carry = skew % tiles_x;
+    }
+    __host__ __device__ bool done() const { return tile >= tile_end; }
+    __host__ __device__ void advance()
+    {
+        tile += step;
+        bx += d_bx;
+        const bool wrap = bx >= tiles_x;
+        bx -= wrap ? tiles_x : 0;
+        by += d_by + (wrap ? 1 : 0);
+        sk += d_sk + (wrap ? sk_carry : 0);          // < 3 tiles_x
+        sk -= sk >= tiles_x ? tiles_x : 0;
+        sk -= sk >= tiles_x ? tiles_x : 0;
+    }
+    __host__ __device__ void origin(int row_begin, int& I0, int& J0) const
+    {
+        int col = bx + sk;
+        col -= col >= tiles_x ? tiles_x : 0;
+        I0 = row_begin + by * MF_T;
+        J0 = col * MF_T;
+    }
+};
+
+// maximum over the wave of the bit patterns of non-negative floats, which order as unsigned integers; valid in lane 63.  The
+// integer maximum takes its DPP operand directly: no canonicalisation and no separate move (wave_max_nonneg has both).
+__device__ __forceinline__ unsigned wave_max_bits(unsigned v)
+{
+#define CS_DPP_UMAX(ctrl, rmask) v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xf, true))
+    CS_DPP_UMAX(0x111, 0xf);      // row_shr:1
+    CS_DPP_UMAX(0x112, 0xf);      // row_shr:2
+    CS_DPP_UMAX(0x114, 0xf);      // row_shr:4
+    CS_DPP_UMAX(0x118, 0xf);      // row_shr:8   -> lane 15 of every row holds the row's maximum
+    CS_DPP_UMAX(0x142, 0xa);      // row_bcast:15 into rows 1 and 3
+    CS_DPP_UMAX(0x143, 0xc);      // row_bcast:31 into rows 2 and 3
+#undef CS_DPP_UMAX
+    return v;
+}
 
 __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDenseArgs A)
 {
@@ -58,34 +130,29 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
     }
     const f4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
     const int wr0 = 16 * (wv & 3), wc0 = 32 * (wv >> 2);      // the wave's rows and columns of the tile
-    const int c2 = tid % 40, rg = tid / 40;                  // staging: column pair, row group (threads >= 480 idle)
-    const bool stager = tid < 480;
+    // staging: column pair, row group.  Thread t reads and splits the rows rg + 12 k.  No lane is masked: the threads 480 .. 511
+    // (rg = 12) repeat rows of row group 0 -- the same pixels give the same maximum, the same four float16 values and the same
+    // bytes at the same plane addresses -- and the seventh row, rg + 72, exists for whole waves or not at all: rg <= 7 in the
+    // waves 0 .. 4 (threads < 320), rg >= 8 in the others.
+    const int c2 = tid % 40, rg = tid / 40;
+    static_assert(12 + 12 * (MF8_ROWS_PER_THREAD - 2) < MF_R && 319 / 40 + 72 == MF_R - 1 && 320 / 40 + 72 == MF_R, "staging rows");
     // input rows that windows of [row_begin, row_end) reach and that exist
     const int p_min = max(0, A.row_begin - KH), p_max = min(A.ms, A.row_end + (K - 1) - KH) - 1;
 
-    // tile order of the 4-wave instance: row-major, tile row `by` skewed by `by * skew` columns (dense_tile_skew)
-    auto tile_origin = [&](int tile, int& I0, int& J0) {
-        const int by = tile / A.tiles_x;
-        int bx = tile - by * A.tiles_x;
-        const int skew = A.xcd_order >> 1;
-        if (skew) {
-            bx += (by * skew) % A.tiles_x;
-            bx -= bx >= A.tiles_x ? A.tiles_x : 0;
-        }
-        I0 = A.row_begin + by * MF_T;
-        J0 = bx * MF_T;
+    // every staged pixel of the tile at (I0, J0) exists: its transfers are not clamped and its reader needs no masks
+    auto tile_inside = [&](int I0, int J0) {
+        const int P0 = I0 - KH, Q0 = J0 - KH;
+        return P0 >= p_min && P0 + MF_R - 1 <= p_max && Q0 >= 0 && Q0 + MF_R <= A.ns;
     };
     // LDS-DMA of one tile's 80 x 80 pixels in 16-byte pieces (20 per row): a wave-wide transfer moves 64 consecutive pieces, wave
     // w issues the transfers w, w + 8, ...; a lane's piece advances by 512 pieces -- 25 rows and 12 pieces -- per step.
     const int wv_u = __builtin_amdgcn_readfirstlane(wv);
-    auto fetch = [&](int tile) {
-        int I0, J0;
-        tile_origin(tile, I0, J0);
+    auto fetch = [&](int I0, int J0, bool inside) {
         const int P0 = I0 - KH, Q0 = J0 - KH;
         const int e0 = 64 * wv_u + lane;
         int r = e0 / 20, c = e0 - r * 20;
         const lds_char* dst = (const lds_char*)(raw) + 1024 * wv_u;
-        if (P0 >= p_min && P0 + MF_R - 1 <= p_max && Q0 >= 0 && Q0 + MF_R <= A.ns) {
+        if (inside) {
             // inner tiles (nearly all): no clamp can bite, a piece's address is one base + r ld + 4 c
             const float* src = A.sig + ((long long)P0 + r - A.row0_in) * A.ld_in + Q0 + 4 * c;
             const long long step_r = 25 * A.ld_in + 48, wrap = A.ld_in - 80;
@@ -229,20 +296,18 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
 #pragma unroll
     for (int c = 0; c < 2; ++c) p_acc[c] = p_S1[c] = p_S2[c] = zero4;
 
-    // Tile sequence of this workgroup: XCD x takes the tiles [x n / 8, (x + 1) n / 8) and its workgroups walk that range side
-    // by side (see cs_corr_mfma_body.inc)
-    int tile, tile_end, tile_step;
-    if ((A.xcd_order & 1) && gridDim.x % 8 == 0) {
-        const int x = blockIdx.x & 7, per = (A.n_tiles + 7) / 8;
-        tile = x * per + (blockIdx.x >> 3);
-        tile_end = min(A.n_tiles, (x + 1) * per);
-        tile_step = gridDim.x >> 3;
-    } else {
-        tile = blockIdx.x;
-        tile_end = A.n_tiles;
-        tile_step = gridDim.x;
+    // Tile sequence of this workgroup (DenseTileWalk).  A tile's origin and its `inside` are formed once, where its transfers are
+    // issued, and handed to the iteration that computes it.
+    DenseTileWalk walk;
+    walk.init(A.tiles_x, A.n_tiles, (int)gridDim.x, A.xcd_order, (int)blockIdx.x);
+    bool have = !walk.done();
+    int I0 = 0, J0 = 0;
+    bool inside = false;
+    if (have) {                                  // the first tile is on its way while the weights are loaded
+        walk.origin(A.row_begin, I0, J0);
+        inside = tile_inside(I0, J0);
+        fetch(I0, J0, inside);
     }
-    if (tile < tile_end) fetch(tile);            // the first tile is on its way while the weights are loaded
 
     // ---- weights: nine rows of tails (slots 0 .. 8) and nine rows of heads (slots 9 .. 17) as ready-made fragments; row s > 8 is
     //      row 16 - s.  18 x 64 fragments of 16 bytes, up to three per thread.
@@ -263,12 +328,13 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         }
     }
     MF_WALL(12);
-    for (; tile < tile_end; tile += tile_step) {
-        int I0, J0;
-        tile_origin(tile, I0, J0);
+    // waves whose threads stage a seventh row (see c2, rg)
+    const bool row7 = wv_u < 5;
+    // The waves 4 .. 7 are dispatched behind the waves 0 .. 3 and lose the arbitration by age in every phase: one static priority
+    // for that half (s_setprio ignores EXEC: the condition is on a scalar).
+    if (wv_u >= 4) __builtin_amdgcn_s_setprio(1);
+    while (have) {
         const int P0 = I0 - KH, Q0 = J0 - KH;
-        // every staged pixel exists: the transfers were not clamped and the reader needs no masks
-        const bool inside = P0 >= p_min && P0 + MF_R - 1 <= p_max && Q0 >= 0 && Q0 + MF_R <= A.ns;
 #ifdef CS_MF_PROFILE
         tprev_ = __builtin_readcyclecounter();
         if (tid == 0) prof_lds[15] += 1ull;
@@ -278,36 +344,34 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         lds_barrier();                           // everyone's transfers; the previous tile's plane readers are done
         float xa[MF8_ROWS_PER_THREAD], xb[MF8_ROWS_PER_THREAD];
         float amax = 0.0f;
+        xa[MF8_ROWS_PER_THREAD - 1] = xb[MF8_ROWS_PER_THREAD - 1] = 0.0f;
         if (inside) {
 #pragma unroll
             for (int k = 0; k < MF8_ROWS_PER_THREAD; ++k) {
-                const int r = rg + 12 * k;
-                float2 v = make_float2(0.0f, 0.0f);
-                if (stager && r < MF_R) v = *reinterpret_cast<const float2*>(raw + r * MF_R + 2 * c2);
-                xa[k] = v.x;
-                xb[k] = v.y;
-                amax = fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y)));
+                if (k < MF8_ROWS_PER_THREAD - 1 || row7) {
+                    const float2 v = *reinterpret_cast<const float2*>(raw + (rg + 12 * k) * MF_R + 2 * c2);
+                    xa[k] = v.x;
+                    xb[k] = v.y;
+                    amax = fmaxf(amax, fmaxf(fabsf(v.x), fabsf(v.y)));
+                }
             }
         } else {
 #pragma unroll
             for (int k = 0; k < MF8_ROWS_PER_THREAD; ++k) {
-                const int r = rg + 12 * k;
-                float a = 0.0f, b = 0.0f;
-                if (stager && r < MF_R) {
+                if (k < MF8_ROWS_PER_THREAD - 1 || row7) {
+                    const int r = rg + 12 * k;
                     const float2 v = *reinterpret_cast<const float2*>(raw + r * MF_R + 2 * c2);
                     const int p = P0 + r, q = Q0 + 2 * c2;
                     const bool rok = (p >= p_min) & (p <= p_max);
                     const bool oka = rok & (q >= 0) & (q < A.ns), okb = rok & (q + 1 >= 0) & (q + 1 < A.ns);
-                    a = oka ? v.x : 0.0f;
-                    b = okb ? v.y : 0.0f;
+                    xa[k] = oka ? v.x : 0.0f;
+                    xb[k] = okb ? v.y : 0.0f;
+                    amax = fmaxf(amax, fmaxf(fabsf(xa[k]), fabsf(xb[k])));
                 }
-                xa[k] = a;
-                xb[k] = b;
-                amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(b)));
             }
         }
-        amax = wave_max_nonneg(amax);
-        if (lane == 63) red[wv] = __float_as_uint(amax);
+        const unsigned amax_bits = wave_max_bits(__float_as_uint(amax));
+        if (lane == 63) red[wv] = amax_bits;
         MF_STAMP(0);
         lds_barrier();                           // everyone has read `raw`: the squares may overwrite it
         int ex = 0;
@@ -324,8 +388,8 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         typedef __fp16 hv2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int k = 0; k < MF8_ROWS_PER_THREAD; ++k) {
-            const int r = rg + 12 * k;
-            if (stager && r < MF_R) {
+            if (k < MF8_ROWS_PER_THREAD - 1 || row7) {
+                const int r = rg + 12 * k;
                 // heads by truncation, tails exact differences (one v_fma_mix_f32 per value from the packed heads)
                 const float a = xa[k] * scale, b = xb[k] * scale;
                 const hv2 hh = __builtin_amdgcn_cvt_pkrtz(a, b);
@@ -398,7 +462,15 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         MF_STAMP(2);
         lds_barrier();                           // all waves are done with the squares
         // ---- next tile's pixels -> `raw` while this tile's correlation runs
-        if (tile + tile_step < tile_end) fetch(tile + tile_step);
+        walk.advance();
+        const bool have_next = !walk.done();
+        int n_I0 = 0, n_J0 = 0;
+        bool n_inside = false;
+        if (have_next) {
+            walk.origin(A.row_begin, n_I0, n_J0);
+            n_inside = tile_inside(n_I0, n_J0);
+            fetch(n_I0, n_J0, n_inside);
+        }
 
         MF_STAMP(3);
         // ---- cross term: 17 template rows x 2 column tiles, fragments of row s + 1 in flight during row s
@@ -456,6 +528,10 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         p_J0 = J0;
         p_unscale = unscale;
         pending = true;
+        I0 = n_I0;
+        J0 = n_J0;
+        inside = n_inside;
+        have = have_next;
     }
     MF_WALL(13);
     if (pending) emit(p_I0, p_J0, p_unscale, p_acc, p_S1, p_S2);

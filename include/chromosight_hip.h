@@ -99,6 +99,12 @@ int cs_last_kernel(const cs_ctx* ctx);
  * whose rows mirror; four waves per SIMD) and 4 waves (every other dense call, or CHROMOSIGHT_HIP_MFMA_WAVES4=1).  Returns 8 or 4,
  * or 0 when the dense tile kernel did not serve the last call. */
 int cs_last_dense_waves(const cs_ctx* ctx);
+/* The tile sequence of one workgroup of the 8-wave instance, from the division-free walk the kernel uses: the origins (first output
+ * row and column) of the tiles that workgroup `block` of `grid` computes, in order, for a map of `n_tiles` tiles in rows of
+ * `tiles_x`, with the launcher's `xcd_order` (bit 0: contiguous ranges per XCD; bits 1-2: column skew per tile row) and first row
+ * `row_begin`.  Fills at most `cap` entries of i0 / j0 and returns the number of tiles of the workgroup, -1 on bad arguments.
+ * Needs no device. */
+int cs_dense_tile_walk(int tiles_x, int n_tiles, int grid, int xcd_order, int row_begin, int block, int* i0, int* j0, int cap);
 /* Range guard of the device entries (off by default).  The reference sums every window on its own
  * (detection.py:1002-1018) and zeroes exactly the windows that hold a non-finite pixel (:1088-1101); the device kernels
  * keep running box sums and square in float32, so a DEVICE-RESIDENT map handed to cs_normxcorr2 must be finite and, for
