@@ -1185,18 +1185,37 @@ int cs_label_foci(cs_ctx* ctx, void* stream_, int32_t ms, int32_t ns, const int3
                   const double* h_vals, int64_t n, int32_t min_size, int32_t diag_only, int32_t* h_foci_rows,
                   int32_t* h_foci_cols, int32_t* h_foci_size, int64_t cap, int64_t* n_foci)
 {
+    return cs_label_foci_route(ctx, stream_, ms, ns, h_rows, h_cols, h_vals, n, min_size, diag_only, 0, h_foci_rows, h_foci_cols,
+                               h_foci_size, cap, n_foci);
+}
+
+int cs_label_foci_route(cs_ctx* ctx, void* stream_, int32_t ms, int32_t ns, const int32_t* h_rows, const int32_t* h_cols,
+                        const double* h_vals, int64_t n, int32_t min_size, int32_t diag_only, int32_t route,
+                        int32_t* h_foci_rows, int32_t* h_foci_cols, int32_t* h_foci_size, int64_t cap, int64_t* n_foci)
+{
     CS_ENTER(ctx);
     hipStream_t stream = (hipStream_t)stream_;
     if (!n_foci || n < 0 || ms <= 0 || ns <= 0 || min_size < 1 || (n > 0 && (!h_rows || !h_cols || !h_vals)))
         return fail(ctx, CS_ERR_INVALID, "bad candidate list");
     if (cap < 0 || (cap > 0 && (!h_foci_rows || !h_foci_cols || !h_foci_size))) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
     if (n > INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%lld)", (long long)n);
+    // the forms of the labelling (route 0: what cs_label_foci runs) and the lists each takes -- refused before anything is launched
+    if (route < 0 || route > 3) return fail(ctx, CS_ERR_INVALID, "unknown labelling route %d", (int)route);
+    if (route == 1 && n > cs::kFociSmallMax)
+        return fail(ctx, CS_ERR_UNSUPPORTED, "%lld candidate pixels: one workgroup takes %lld", (long long)n, cs::kFociSmallMax);
+    if (route >= 2 && n > cs::kFociSmallLds)
+        return fail(ctx, CS_ERR_UNSUPPORTED, "%lld candidate pixels: the LDS form takes %d", (long long)n, cs::kFociSmallLds);
+    if (route >= 2 && (unsigned long long)ms * (unsigned long long)ns > 0xffffffffull)
+        return fail(ctx, CS_ERR_UNSUPPORTED, "the LDS form keeps 32-bit keys: %d x %d pixels", (int)ms, (int)ns);
     *n_foci = 0;
     if (n == 0) return CS_OK;
     if (!ctx->h_counts) CS_HIP(ctx, hipHostMalloc((void**)&ctx->h_counts, 64, hipHostMallocDefault));
     for (int64_t t = 0; t < n; ++t)
         if (h_rows[t] < 0 || h_rows[t] >= ms || h_cols[t] < 0 || h_cols[t] >= ns)
             return fail(ctx, CS_ERR_INVALID, "candidate %lld outside the matrix", (long long)t);
+    if (route != 0)                 // (the one-workgroup forms threshold their list and drop exact zeros: not the list given)
+        for (int64_t t = 0; t < n; ++t)
+            if (h_vals[t] == 0.0) return fail(ctx, CS_ERR_INVALID, "candidate %lld has the value 0", (long long)t);
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t un = (size_t)n;
     const size_t off_cols = al(4 * un), off_vals = off_cols + al(4 * un), off_cnt = off_vals + al(8 * un),
@@ -1209,8 +1228,8 @@ int cs_label_foci(cs_ctx* ctx, void* stream_, int32_t ms, int32_t ns, const int3
     CS_HIP(ctx, hipMemcpyAsync(pool + off_vals, h_vals, 8 * un, hipMemcpyHostToDevice, stream));
     long long* d_cnt = (long long*)(pool + off_cnt);
     int *f_rows = nullptr, *f_cols = nullptr, *f_size = nullptr;
-    rc = cs::enqueue_label((const int*)pool, (const int*)(pool + off_cols), (const double*)(pool + off_vals), n, ns, min_size,
-                           diag_only, pool + off_tail, &f_rows, &f_cols, &f_size, d_cnt, stream);
+    rc = cs::enqueue_label_route((const int*)pool, (const int*)(pool + off_cols), (const double*)(pool + off_vals), n, ns, min_size,
+                                 diag_only, route, pool + off_tail, &f_rows, &f_cols, &f_size, d_cnt, stream);
     if (rc) return fail(ctx, CS_ERR_HIP, "labelling kernels failed: %s", hipGetErrorString((hipError_t)rc));
     CS_HIP(ctx, hipMemcpyAsync(ctx->h_counts + 1, d_cnt, 8, hipMemcpyDeviceToHost, stream));
     CS_HIP(ctx, hipStreamSynchronize(stream));

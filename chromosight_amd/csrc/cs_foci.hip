@@ -236,35 +236,61 @@ size_t label_scratch_bytes(long long n)
     return al(std::max(sort_tmp, scan_tmp)) + 2 * al(8 * m) + 3 * al(8 * m) + 10 * al(4 * m) + 1024;
 }
 
-// candidates with their float64 values (device arrays, any order) -> foci in the reference's order:
-// (row, col) of the maximum of every focus of >= min_size pixels and its size; *d_n_foci on the device
-int enqueue_label(const int* d_rows, const int* d_cols, const double* d_vals, long long n, int ns, int min_size,
-                  int diag_only, void* scratch, int** f_rows_out, int** f_cols_out, int** f_size_out,
-                  long long* d_n_foci, hipStream_t stream)
+// the arrays of a labelling carved from label_scratch_bytes(n) bytes
+namespace {
+struct LabelScratch {
+    void* tmp;
+    size_t tmp_bytes;
+    long long *keys, *keys_s;
+    double* vals_s;
+    unsigned long long* best_val;
+    double* vals_k;                 // (the one-workgroup form's kept values; the kernel chain leaves it alone)
+    int *flag, *pos, *parent, *size, *best_idx, *f_rows, *f_cols, *f_size, *n_dev;
+};
+
+LabelScratch carve_label_scratch(void* scratch, long long n)
 {
     Bump b{(char*)scratch};
     size_t sort_tmp = 0, scan_tmp = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const long long*)nullptr, (long long*)nullptr,
                                              (const double*)nullptr, (double*)nullptr, (int)n);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int*)nullptr, (int*)nullptr, (int)n);
-    size_t tmp_bytes = std::max(sort_tmp, scan_tmp);
-    void* tmp = b.take<char>(tmp_bytes);
+    LabelScratch L;
+    L.tmp_bytes = std::max(sort_tmp, scan_tmp);
+    L.tmp = b.take<char>(L.tmp_bytes);
     const size_t m = (size_t)n;
-    long long* keys = b.take<long long>(m);
-    long long* keys_s = b.take<long long>(m);
-    double* vals_s = b.take<double>(m);
-    unsigned long long* best_val = b.take<unsigned long long>(m);
-    double* spare = b.take<double>(m);
-    (void)spare;
-    int* flag = b.take<int>(m);
-    int* pos = b.take<int>(m);
-    int* parent = b.take<int>(m);
-    int* size = b.take<int>(m);
-    int* best_idx = b.take<int>(m);
-    int* f_rows = b.take<int>(m);
-    int* f_cols = b.take<int>(m);
-    int* f_size = b.take<int>(m);
-    int* n_dev = b.take<int>(64);
+    L.keys = b.take<long long>(m);
+    L.keys_s = b.take<long long>(m);
+    L.vals_s = b.take<double>(m);
+    L.best_val = b.take<unsigned long long>(m);
+    L.vals_k = b.take<double>(m);
+    L.flag = b.take<int>(m);
+    L.pos = b.take<int>(m);
+    L.parent = b.take<int>(m);
+    L.size = b.take<int>(m);
+    L.best_idx = b.take<int>(m);
+    L.f_rows = b.take<int>(m);
+    L.f_cols = b.take<int>(m);
+    L.f_size = b.take<int>(m);
+    L.n_dev = b.take<int>(64);
+    return L;
+}
+}  // namespace
+
+// candidates with their float64 values (device arrays, any order) -> foci in the reference's order:
+// (row, col) of the maximum of every focus of >= min_size pixels and its size; *d_n_foci on the device
+int enqueue_label(const int* d_rows, const int* d_cols, const double* d_vals, long long n, int ns, int min_size,
+                  int diag_only, void* scratch, int** f_rows_out, int** f_cols_out, int** f_size_out,
+                  long long* d_n_foci, hipStream_t stream)
+{
+    const LabelScratch L = carve_label_scratch(scratch, n);
+    void* const tmp = L.tmp;
+    size_t tmp_bytes = L.tmp_bytes;
+    long long *const keys = L.keys, *const keys_s = L.keys_s;
+    double* const vals_s = L.vals_s;
+    unsigned long long* const best_val = L.best_val;
+    int *const flag = L.flag, *const pos = L.pos, *const parent = L.parent, *const size = L.size, *const best_idx = L.best_idx;
+    int *const f_rows = L.f_rows, *const f_cols = L.f_cols, *const f_size = L.f_size, *const n_dev = L.n_dev;
     *f_rows_out = f_rows;
     *f_cols_out = f_cols;
     *f_size_out = f_size;
@@ -283,6 +309,51 @@ int enqueue_label(const int* d_rows, const int* d_cols, const double* d_vals, lo
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(emit_foci_kernel, dim3(g), dim3(kThreads), 0, stream, n_dev, flag, pos, best_idx, size, keys_s, ns,
                        diag_only, f_rows, f_cols, f_size, n, d_n_foci);
+    return (int)hipGetLastError();
+}
+
+static_assert(kFociSmallMax == kSmallMax && kFociSmallLds == kSmallLds, "the limits the API checks are the kernels'");
+
+// enqueue_label through a chosen form of the labelling (cs_label_foci_route, the test seam): 0 the kernel chain above, 1
+// foci_small_body in one workgroup after the same device sort, 2 foci_small_lds_body on the sorted list, 3 the same on the list
+// as given (unsorted = 1: lds_sort_pairs).  The caller has checked that the form takes the list (n, ms * ns) and that no value
+// is 0; pearson = -infinity keeps every value.  Same scratch as enqueue_label (label_scratch_bytes).
+int enqueue_label_route(const int* d_rows, const int* d_cols, const double* d_vals, long long n, int ns, int min_size,
+                        int diag_only, int route, void* scratch, int** f_rows_out, int** f_cols_out, int** f_size_out,
+                        long long* d_n_foci, hipStream_t stream)
+{
+    if (route == 0)
+        return enqueue_label(d_rows, d_cols, d_vals, n, ns, min_size, diag_only, scratch, f_rows_out, f_cols_out, f_size_out,
+                             d_n_foci, stream);
+    const LabelScratch L = carve_label_scratch(scratch, n);
+    size_t tmp_bytes = L.tmp_bytes;
+    long long* const keys = L.keys;
+    *f_rows_out = L.f_rows;
+    *f_cols_out = L.f_cols;
+    *f_size_out = L.f_size;
+    const double keep_all = -HUGE_VAL;
+    const unsigned g = blocks_for(n);
+    hipLaunchKernelGGL(make_keys_kernel, dim3(g), dim3(kThreads), 0, stream, d_rows, d_cols, n, ns, keys);
+    const long long* list_keys = keys;
+    const double* list_vals = d_vals;
+    if (route != 3) {
+        hipError_t e = hipcub::DeviceRadixSort::SortPairs(L.tmp, tmp_bytes, keys, L.keys_s, d_vals, L.vals_s, (int)n, 0, 64, stream);
+        if (e != hipSuccess) return (int)e;
+        list_keys = L.keys_s;
+        list_vals = L.vals_s;
+    }
+    if (route == 1) {
+        // (the unsorted keys are dead after the sort: their array holds the kept keys)
+        hipLaunchKernelGGL(foci_small_kernel, dim3(1), dim3(kSmallThreads), 0, stream, list_keys, list_vals, n, keep_all, ns, min_size,
+                           diag_only, L.flag, L.pos, keys, L.vals_k, L.parent, L.size, L.best_val, L.best_idx, L.f_rows, L.f_cols,
+                           L.f_size, L.n_dev, d_n_foci);
+        return (int)hipGetLastError();
+    }
+    hipError_t e = hipFuncSetAttribute((const void*)foci_small_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmallLdsBytes);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(foci_small_lds_kernel, dim3(1), dim3(kSmallThreads), kSmallLdsBytes, stream, list_keys, list_vals, (int)n,
+                       keep_all, (unsigned)ns, min_size, diag_only, L.best_val, L.f_rows, L.f_cols, L.f_size, L.n_dev, d_n_foci,
+                       route == 3 ? 1 : 0);
     return (int)hipGetLastError();
 }
 

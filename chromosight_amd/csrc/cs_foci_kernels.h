@@ -117,10 +117,11 @@ __global__ __launch_bounds__(kThreads) void link_kernel(const long long* __restr
     if (lo < n && keys[lo] == want) uf_union(parent, (int)t, (int)lo);
 }
 
-// root of x without writing: flatten_kernel must not halve paths.  A halving store parent[x] = gp of one thread can land
-// after another thread's final parent[x] = root, leaving x under a non-root ancestor: focus_stats_kernel then splits the focus
-// and reports the best pixel of a part (seen: 1 focus in ~50 labellings of a 16 671-pixel list).  Read-only walks only ever see
-// ancestors or the root, and every store here is a root.
+// root of x without writing: the flatten phases (flatten_kernel, foci_small_body, foci_small_lds_body) must not halve paths.  A
+// halving store parent[x] = gp of one thread can land after another thread's final parent[x] = root, leaving x under a non-root
+// ancestor: the statistics phase then splits the focus and reports the best pixel of a part (seen: 1 focus in ~50 labellings of a
+// 16 671-pixel list through flatten_kernel; up to 72 of 100 labellings of an 8189-pixel snake through the one-workgroup forms).
+// Read-only walks only ever see ancestors or the root, and every store of those phases is a root.
 __device__ __forceinline__ int uf_root(const int* parent, int x)
 {
     int p = uf_load(parent + x);
@@ -295,7 +296,12 @@ __device__ __forceinline__ void foci_small_body(
         if (lo < n && keys_k[lo] == want) uf_union(parent, t, (int)lo);
     }
     __syncthreads();
-    for (int t = tid; t < n; t += kSmallThreads) parent[t] = uf_find(parent, t);
+    // flatten with the read-only walk, as flatten_kernel does: the waves of a workgroup run concurrently, and a halving store
+    // parent[x] = gp of one thread's uf_find (gp read earlier) could land after the owner's final parent[x] = root and leave x
+    // under a non-root ancestor -- the next phase takes parent[t] for the root and would split the focus.  No union runs in this
+    // phase, so the roots are fixed; every store writes a root, so a walk only ever reads an ancestor or the root and ends at the
+    // root whatever the order of the stores.
+    for (int t = tid; t < n; t += kSmallThreads) __atomic_store_n(parent + t, uf_root(parent, t), __ATOMIC_RELAXED);
     __syncthreads();
     for (int t = tid; t < n; t += kSmallThreads) {
         const int r = parent[t];
@@ -831,7 +837,9 @@ __device__ __forceinline__ void foci_small_lds_body(
         if (lo < n && s_key[lo] == want) uf_union(s_parent, t, lo);
     }
     __syncthreads();
-    for (int t = tid; t < n; t += kSmallThreads) s_parent[t] = uf_find(s_parent, t);
+    // read-only walk, every store a root (see foci_small_body and uf_root): a halving store of another wave's uf_find must not
+    // be able to overwrite a final s_parent[t] = root with a stale ancestor
+    for (int t = tid; t < n; t += kSmallThreads) __atomic_store_n(s_parent + t, uf_root(s_parent, t), __ATOMIC_RELAXED);
     __syncthreads();
     for (int t = tid; t < n; t += kSmallThreads) {
         const int r = s_parent[t];
@@ -891,6 +899,19 @@ __global__ __launch_bounds__(kSmallThreads) void foci_small_batch_kernel(
     foci_small_body(keys_s + o, vals + o, n_cand, pearson, tab[b].ns, min_size, diag_only, flag + o, pos + o, keys_k + o, vals_k + o,
                     parent + o, size + o, best_val + o, best_idx + o, out_rows + o, out_cols + o, out_size + o, n_kept + b,
                     n_foci_blk + b, part);
+}
+
+// foci_small_lds_body on ONE candidate list (cs_label_foci_route, routes 2 and 3: the test seam that hands the LDS form a list of
+// known shape); kSmallLdsBytes of dynamic LDS
+__global__ __launch_bounds__(kSmallThreads) void foci_small_lds_kernel(
+    const long long* __restrict__ keys_s, const double* __restrict__ vals, int n_cand, double pearson, unsigned ns, int min_size,
+    int diag_only, unsigned long long* __restrict__ best_val, int* __restrict__ out_rows, int* __restrict__ out_cols,
+    int* __restrict__ out_size, int* __restrict__ n_kept_out, long long* __restrict__ n_foci, int unsorted)
+{
+    __shared__ int part[32];
+    extern __shared__ __attribute__((aligned(16))) char small_lds[];     // kSmallLdsBytes
+    foci_small_lds_body(keys_s, vals, n_cand, pearson, ns, min_size, diag_only, best_val, out_rows, out_cols, out_size, n_kept_out,
+                        n_foci, part, small_lds, unsorted);
 }
 
 // dynamic LDS of foci_small_batch_kernel (0: CHROMOSIGHT_HIP_NO_LDS_FOCI, every list through the global arrays)

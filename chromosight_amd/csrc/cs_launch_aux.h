@@ -887,6 +887,12 @@ size_t label_scratch_bytes(long long n);
 int enqueue_label(const int* d_rows, const int* d_cols, const double* d_vals, long long n, int ns, int min_size,
                   int diag_only, void* scratch, int** f_rows_out, int** f_cols_out, int** f_size_out,
                   long long* d_n_foci, hipStream_t stream);
+// the same through one chosen form of the labelling (cs_label_foci_route): 0 kernel chain, 1 one workgroup on global arrays,
+// 2 / 3 one workgroup with its arrays in LDS on the sorted list / on the list as given
+constexpr int kFociSmallLds = 8192;                // candidates the LDS form takes (and ms * ns <= 2^32 - 1)
+int enqueue_label_route(const int* d_rows, const int* d_cols, const double* d_vals, long long n, int ns, int min_size,
+                        int diag_only, int route, void* scratch, int** f_rows_out, int** f_cols_out, int** f_size_out,
+                        long long* d_n_foci, hipStream_t stream);
 
 // 1-D patterns: all pixels of a band of a few diagonals as the candidate list (cs_foci.hip)
 long long narrow_band_pixels(int rb, int re, int ns, int lo, int w);      // rows rb <= i < re

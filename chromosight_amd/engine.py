@@ -454,19 +454,22 @@ def run_candidates_tiles(dev, sig, shape, kspec, row_window, tiles, n_tiles, *, 
 
 
 @_one_call_per_context
-def run_label_foci(dev, shape, rows, cols, vals, *, min_size=2, diag_only=False, stream=None):
+def run_label_foci(dev, shape, rows, cols, vals, *, min_size=2, diag_only=False, stream=None, route=0, cap=None):
     """Second half of detect mode (cs_label_foci): the 4-connected foci of a candidate list -- the
-    coordinates of each focus at its maximum and its size, in the order of cs_detect_foci."""
+    coordinates of each focus at its maximum and its size, in the order of cs_detect_foci.
+    route: the form of the device labelling (cs_label_foci_route; 0 = what cs_label_foci runs); cap: room for the foci
+    (default: as many as the list can hold)."""
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     cols = np.ascontiguousarray(cols, dtype=np.int32)
     vals = np.ascontiguousarray(vals, dtype=np.float64)
     k = rows.size
-    cap = max(k // max(int(min_size), 1), 1)
-    f_rows, f_cols, f_size = (np.empty(cap, np.int32) for _ in range(3))
+    if cap is None:
+        cap = max(k // max(int(min_size), 1), 1)
+    f_rows, f_cols, f_size = (np.empty(max(cap, 1), np.int32) for _ in range(3))
     n = C.c_int64(0)
-    dev._check(dev.lib.cs_label_foci(dev.ctx, stream, int(shape[0]), int(shape[1]), rows.ctypes.data, cols.ctypes.data,
-                                     vals.ctypes.data, k, int(min_size), int(diag_only), f_rows.ctypes.data,
-                                     f_cols.ctypes.data, f_size.ctypes.data, cap, C.byref(n)))
+    dev._check(dev.lib.cs_label_foci_route(dev.ctx, stream, int(shape[0]), int(shape[1]), rows.ctypes.data, cols.ctypes.data,
+                                           vals.ctypes.data, k, int(min_size), int(diag_only), int(route), f_rows.ctypes.data,
+                                           f_cols.ctypes.data, f_size.ctypes.data, int(cap), C.byref(n)))
     m = int(n.value)
     return f_rows[:m], f_cols[:m], f_size[:m]
 

@@ -586,14 +586,26 @@ int cs_quantify_blocks(cs_ctx* ctx, void* stream, int32_t n_blocks, const cs_mat
  *
  * cs_label_foci: the 4-connected foci of a candidate list (the concatenation of every window's
  * candidates, any order): coordinates of each focus of >= min_size pixels at its maximum (row = col when
- * diag_only) and its size, in row-major order of the maxima's first pixels, exactly the foci cs_detect_foci
- * finds on the whole map.  Their records follow from cs_quantify_pixels on the window that owns the row. */
+ * diag_only) and its size, in the row-major order of each focus's first pixel (the reference's label order), exactly
+ * the foci cs_detect_foci finds on the whole map.  Their records follow from cs_quantify_pixels on the window that owns the row.
+ * The list holds distinct pixels of the matrix with finite nonzero values (the callers concatenate disjoint row windows of kept
+ * candidates). */
 int cs_candidates(cs_ctx* ctx, void* stream, const cs_matrix* signal, const cs_kernel* kernel,
                   const cs_normxcorr2_params* params, const cs_foci_params* foci, int32_t* h_rows,
                   int32_t* h_cols, double* h_vals, int64_t cap, int64_t* n);
 int cs_label_foci(cs_ctx* ctx, void* stream, int32_t ms, int32_t ns, const int32_t* h_rows,
                   const int32_t* h_cols, const double* h_vals, int64_t n, int32_t min_size, int32_t diag_only,
                   int32_t* h_foci_rows, int32_t* h_foci_cols, int32_t* h_foci_size, int64_t cap, int64_t* n_foci);
+/* Test seam: cs_label_foci through ONE chosen form of the device labelling (the product picks a form by the length of the list;
+ * this hands each of them a list of known shape).  route 0: the kernel chain, any n (= cs_label_foci); 1: one workgroup on
+ * global arrays after the same device sort, n <= 65 536; 2: one workgroup with its arrays in LDS on the sorted list, n <= 8192
+ * and ms * ns <= 2^32 - 1; 3: the same on the list as given, sorted in LDS.  A list the form does not take is refused with
+ * CS_ERR_UNSUPPORTED, an unknown route or (routes 1-3, which would drop it) a value of 0 with CS_ERR_INVALID, before anything
+ * is launched.  Same outputs and errors as cs_label_foci otherwise. */
+int cs_label_foci_route(cs_ctx* ctx, void* stream, int32_t ms, int32_t ns, const int32_t* h_rows,
+                        const int32_t* h_cols, const double* h_vals, int64_t n, int32_t min_size, int32_t diag_only,
+                        int32_t route, int32_t* h_foci_rows, int32_t* h_foci_cols, int32_t* h_foci_size, int64_t cap,
+                        int64_t* n_foci);
 
 /* ---- Trans blocks in row strips: only the tiles a stored pixel reaches.
  *
