@@ -286,6 +286,10 @@ _PROTOTYPES = {
     "cs_quantify_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                      C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_int64, C.c_void_p, C.c_void_p]),
+    "cs_pileup_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CsMatrix), C.POINTER(CsKernel),
+                                   C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p]),
+    "cs_pileup_chunk": (C.c_int64, [C.c_int64]),
     "cs_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                 C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),

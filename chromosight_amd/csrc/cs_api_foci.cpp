@@ -1331,4 +1331,62 @@ int cs_quantify_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs_ma
     return CS_OK;
 }
 
+// the pileup of the windows at n pixels, summed on the device in a fixed order (cs_pileup.hip): the arguments of
+// cs_quantify_blocks; h_sum / h_cnt: km * kn entries each
+int64_t cs_pileup_chunk(int64_t n) { return (int64_t)cs::pileup_chunk(n < 0 ? 0 : (long long)n); }
+
+int cs_pileup_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs_matrix* signals, const cs_kernel* kernel,
+                     const cs_normxcorr2_params* params, const cs_foci_params* foci, const int32_t* h_blk, const int32_t* h_rows,
+                     const int32_t* h_cols, int64_t n, double* h_sum, int64_t* h_cnt)
+{
+    CS_ENTER(ctx);
+    AllowLazy allow_lazy(ctx);       // (the windows of the detection path's blocks: lazily evaluated bands included)
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_blocks <= 0 || !signals || !kernel || !params || !foci || !h_sum || !h_cnt) return fail(ctx, CS_ERR_INVALID, "bad batch arguments");
+    if (n < 0 || (n > 0 && (!h_blk || !h_rows || !h_cols))) return fail(ctx, CS_ERR_INVALID, "bad pixel list");
+    if (n > INT32_MAX) return fail(ctx, CS_ERR_OVERFLOW, "too many pixels (%lld)", (long long)n);
+    for (int b = 0; b < n_blocks; ++b) {
+        int rc = check_foci_args(ctx, signals + b, kernel, params + b, foci + b);
+        if (rc) return rc;
+        if (params[b].compute_dtype != CS_F64) return fail(ctx, CS_ERR_UNSUPPORTED, "windows are read in float64");
+    }
+    for (int64_t t = 0; t < n; ++t)
+        if (h_blk[t] < 0 || h_blk[t] >= n_blocks) return fail(ctx, CS_ERR_INVALID, "pixel %lld names sub-matrix %d of %d", (long long)t, h_blk[t], n_blocks);
+    const int kk = kernel->km * kernel->kn;
+    const size_t ukk = (size_t)kk;
+    if (n == 0) {
+        for (size_t e = 0; e < ukk; ++e) h_sum[e] = 0.0, h_cnt[e] = 0;
+        return CS_OK;
+    }
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t un = (size_t)n, nb = (size_t)n_blocks, nc = (size_t)cs::pileup_chunks(n);
+    const size_t off_rows = al(4 * un), off_cols = off_rows + al(4 * un), off_inter = off_cols + al(4 * un),
+                 off_tab = off_inter + al(4 * nb), off_psum = off_tab + al(sizeof(cs::CorrArgs<double>) * nb),
+                 off_pcnt = off_psum + al(8 * nc * ukk), off_sum = off_pcnt + al(8 * nc * ukk), off_cnt = off_sum + al(8 * ukk),
+                 total = off_cnt + al(8 * ukk);
+    int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, total);
+    if (rc) return rc;
+    char* pool = (char*)ctx->d_pool;
+    std::vector<cs::CorrArgs<double>> tab(nb);
+    std::vector<int> inter(nb);
+    for (int b = 0; b < n_blocks; ++b) {
+        rc = build_args<double>(ctx, stream, signals + b, kernel, params + b, &tab[(size_t)b]);
+        if (rc) return rc;
+        inter[(size_t)b] = foci[b].inter;
+    }
+    CS_HIP(ctx, hipMemcpyAsync(pool, h_blk, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync(pool + off_rows, h_rows, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync(pool + off_cols, h_cols, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync(pool + off_inter, inter.data(), 4 * nb, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync(pool + off_tab, tab.data(), sizeof(cs::CorrArgs<double>) * nb, hipMemcpyHostToDevice, stream));
+    rc = cs::enqueue_pileup_batch((const cs::CorrArgs<double>*)(pool + off_tab), (const int*)(pool + off_inter), (const int*)pool,
+                                  (const int*)(pool + off_rows), (const int*)(pool + off_cols), n, kk, (double*)(pool + off_psum),
+                                  (long long*)(pool + off_pcnt), (double*)(pool + off_sum), (long long*)(pool + off_cnt), stream);
+    if (rc) return fail(ctx, CS_ERR_HIP, "pileup kernels failed: %s", hipGetErrorString((hipError_t)rc));
+    CS_HIP(ctx, hipMemcpyAsync(h_sum, pool + off_sum, 8 * ukk, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipMemcpyAsync(h_cnt, pool + off_cnt, 8 * ukk, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipStreamSynchronize(stream));       // (the pageable tables above were consumed)
+    return CS_OK;
+}
+
 }  // extern "C"

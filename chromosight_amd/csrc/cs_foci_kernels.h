@@ -393,13 +393,6 @@ __global__ __launch_bounds__(kThreads) void narrow_enumerate_batch_kernel(const 
     blk[t] = b;
 }
 
-// CHROMOSIGHT_HIP_NO_FAST_WINDOWS=1: the wave-per-window kernels keep the general functions (rescore_pixel, lazy_gather_window)
-// where the compile-time-size ones of cs_launch_aux.h apply -- the two are the same sums in the same order
-static bool fast_windows_on()
-{
-    return std::getenv("CHROMOSIGHT_HIP_NO_FAST_WINDOWS") == nullptr;     // (read per launch: the switch test flips it in-process)
-}
-
 __global__ __launch_bounds__(256) void rescore_batch_kernel(const CorrArgs<double>* __restrict__ tab, const int* __restrict__ blk,
                                                             const int* __restrict__ rows, const int* __restrict__ cols,
                                                             long long n_px, const long long* __restrict__ n_ptr,
@@ -1038,9 +1031,7 @@ __global__ __launch_bounds__(kSmallThreads) void gather_foci_batch_kernel(const 
 
 
 // ---- window statistics of validate_patterns, one wave per pattern --------------------------------
-// The map pattern_detector validates on (detection.py:287-310) is never built: the contact map framed
-// by (kw rows, kh columns) of zeros when full, NaN on the max(km, kn) first sub-diagonals of intra
-// maps, NaN on every row / column that is not a detectable bin; coordinates shifted by (kh, kw).
+// (the window itself, pixel by pixel: cs_launch_aux.h window_frame / window_pixel)
 // window statistics of one pattern by one wave (validate_patterns, detection.py:18-155); rec_out / win_out
 // may be nullptr (beyond the caller's capacity) or page-locked host memory
 // The p-value of a record (reference detection.py:332-336 on the untrimmed map, stats.py:43-81 corr_to_pval: Fisher z, two-sided
@@ -1067,45 +1058,15 @@ __device__ __forceinline__ void window_stats_pattern(const CorrArgs<double>& A, 
                                                      double* lazy_win = nullptr, bool fast_windows = false,
                                                      int have_p0 = INT_MIN, int have_q0 = INT_MIN)
 {
-    const int km = A.km, kn = A.kn, kk = km * kn;
-    const int kh = (km - 1) / 2, kw = (kn - 1) / 2;
-    const int half_h = km / 2 + 1, half_w = kn / 2 + 1;
-    const int pad_r = A.full ? kw : 0, pad_c = A.full ? kh : 0;     // zero_pad_sparse(mat, kh, kw)
-    const int sh_r = A.full ? kh : 0, sh_c = A.full ? kw : 0;       // coords += (kh, kw)
-    const int H = A.ms + 2 * pad_r, W = A.ns + 2 * pad_c;
-    const int big_k = inter ? 0 : max(km, kn);
-    const int p1 = row + sh_r, p2 = col + sh_c;
-    const int high = p1 - half_h + 1, low = p1 + half_h;
-    const int left = p2 - half_w + 1, right = p2 + half_w;
-    const bool inside = (high >= 0) & (low < H) & (left >= 0) & (right < W);   // strict upper bounds (:99-104)
+    const int kk = A.km * A.kn;
+    const WindowFrame F = window_frame(A, inter, row, col, lane, lazy_win, fast_windows, have_p0, have_q0);
+    const bool inside = F.inside;
     int n_zero = 0, n_miss = 0;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    // a lazily evaluated band: the window's pixels gathered by the wave first (cs_launch_aux.h lazy_gather_window)
-    const bool gathered = lazy_win && inside && A.sig.layout == 2 && lazy_window_fits(km, kn);          // wave-uniform
-    // (have_p0, have_q0: lazy_win already holds the window with this top left pixel -- the exact evaluation of the same record
-    // gathered it a moment ago, focus_records_lazy17_kernel)
-    const bool have = gathered && have_p0 == high - pad_r && have_q0 == left - pad_c;
-    if (gathered && !have) {
-        if (fast_windows && km == 17 && kn == 17) lazy_gather_window_sq<17>(A, high - pad_r, left - pad_c, lane, lazy_win);
-        else lazy_gather_window(A, high - pad_r, left - pad_c, lane, lazy_win);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
     for (int e = lane; e < kk; e += 64) {
         double v = nan;
         if (inside) {
-            const int a = e / kn, b = e - a * kn;
-            const int rr = high + a, cc = left + b;
-            const int src_r = rr - pad_r, src_c = cc - pad_c;
-            v = gathered ? lazy_win[e] : load_signal(A, src_r, src_c);       // 0 outside the matrix / stored band
-            const int d = cc - rr;
-            bool miss = (d <= -1) & (d >= -big_k);
-            // framed row rr is detectable iff rr - sh_r is a detectable bin
-            const int br = rr - sh_r, bc = cc - sh_c;
-            miss |= (br < 0) | (br >= A.ms) | (bc < 0) | (bc >= A.ns);
-            if (!miss && A.miss_row) miss = (A.miss_row[br] != 0) | (A.miss_col[bc] != 0);
-            if (miss) v = nan;
+            v = window_pixel(A, F, e, lazy_win);
             const bool fin = (v - v) == 0.0;                     // finite
             n_zero += (fin && v == 0.0) ? 1 : 0;
             n_miss += fin ? 0 : 1;

@@ -1,5 +1,7 @@
 // cs_launch_aux.h -- launchers of the helper kernels in cs_aux.hip (internal).
 #pragma once
+#include <climits>
+#include <cstdlib>
 #include <vector>
 #include "cs_device.h"
 
@@ -746,6 +748,66 @@ __device__ __forceinline__ void rescore_pixel_lane_lds(const CorrArgs<double>& A
         r = pearson_from_sums<double>(cs_, s1, s2, nm, ka, kb, A.ks, masked, &nobs);
     }
 }
+// ---- the window of one pattern, pixel by pixel (validate_patterns, detection.py:18-155) ---------------------------------------------
+// The map pattern_detector validates on (detection.py:287-310) is never built: the contact map framed by (kw rows, kh columns) of
+// zeros when full, NaN on the max(km, kn) first sub-diagonals of intra maps, NaN on every row / column that is not a detectable
+// bin; coordinates shifted by (kh, kw).  window_frame: the geometry of the window of pattern (row, col), by one wave -- and, for a
+// lazily evaluated band whose window fits the wave's LDS slots, the gather of its pixels into lazy_win (lazy_gather_window).
+// window_pixel: pixel e = a * kn + b of a window that is `inside`.  One definition for everything that reads windows: the records
+// and windows of the detect / quantify chains (cs_foci_kernels.h window_stats_pattern) and the pileup (cs_pileup.hip).
+struct WindowFrame {
+    int kn, pad_r, pad_c, sh_r, sh_c, big_k, high, left;
+    bool inside;        // the window lies in the framed map; otherwise it is all NaN (strict upper bounds, :99-104)
+    bool gathered;      // lazy_win holds the window's pixels
+};
+
+// (have_p0, have_q0: lazy_win already holds the window with this top left pixel -- the exact evaluation of the same record
+// gathered it a moment ago, focus_records_lazy17_kernel)
+__device__ __forceinline__ WindowFrame window_frame(const CorrArgs<double>& A, int inter, int row, int col, int lane, double* lazy_win,
+                                                    bool fast_windows, int have_p0 = INT_MIN, int have_q0 = INT_MIN)
+{
+    const int km = A.km, kn = A.kn;
+    const int kh = (km - 1) / 2, kw = (kn - 1) / 2;
+    const int half_h = km / 2 + 1, half_w = kn / 2 + 1;
+    WindowFrame F;
+    F.kn = kn;
+    F.pad_r = A.full ? kw : 0, F.pad_c = A.full ? kh : 0;           // zero_pad_sparse(mat, kh, kw)
+    F.sh_r = A.full ? kh : 0, F.sh_c = A.full ? kw : 0;             // coords += (kh, kw)
+    const int H = A.ms + 2 * F.pad_r, W = A.ns + 2 * F.pad_c;
+    F.big_k = inter ? 0 : max(km, kn);
+    const int p1 = row + F.sh_r, p2 = col + F.sh_c;
+    const int low = p1 + half_h, right = p2 + half_w;
+    F.high = p1 - half_h + 1;
+    F.left = p2 - half_w + 1;
+    F.inside = (F.high >= 0) & (low < H) & (F.left >= 0) & (right < W);
+    // a lazily evaluated band: the window's pixels gathered by the wave first (lazy_gather_window)
+    F.gathered = lazy_win && F.inside && A.sig.layout == 2 && lazy_window_fits(km, kn);          // wave-uniform
+    const bool have = F.gathered && have_p0 == F.high - F.pad_r && have_q0 == F.left - F.pad_c;
+    if (F.gathered && !have) {
+        if (fast_windows && km == 17 && kn == 17) lazy_gather_window_sq<17>(A, F.high - F.pad_r, F.left - F.pad_c, lane, lazy_win);
+        else lazy_gather_window(A, F.high - F.pad_r, F.left - F.pad_c, lane, lazy_win);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    return F;
+}
+
+__device__ __forceinline__ double window_pixel(const CorrArgs<double>& A, const WindowFrame& F, int e, const double* lazy_win)
+{
+    const int a = e / F.kn, b = e - a * F.kn;
+    const int rr = F.high + a, cc = F.left + b;
+    const int src_r = rr - F.pad_r, src_c = cc - F.pad_c;
+    double v = F.gathered ? lazy_win[e] : load_signal(A, src_r, src_c);       // 0 outside the matrix / stored band
+    const int d = cc - rr;
+    bool miss = (d <= -1) & (d >= -F.big_k);
+    // framed row rr is detectable iff rr - sh_r is a detectable bin
+    const int br = rr - F.sh_r, bc = cc - F.sh_c;
+    miss |= (br < 0) | (br >= A.ms) | (bc < 0) | (bc >= A.ns);
+    if (!miss && A.miss_row) miss = (A.miss_row[br] != 0) | (A.miss_col[bc] != 0);
+    if (miss) v = __longlong_as_double(0x7ff8000000000000ll);
+    return v;
+}
 #endif
 
 int launch_distance_law(const CsrView& M, const uint8_t* det, int n_diags, double* d_sum,
@@ -909,6 +971,24 @@ int enqueue_quantify_batch(const CorrArgs<double>* d_tab, const int* d_inter, co
                            long long n, double* d_score, double* d_nobs, FocusRec* d_rec, double* d_windows, hipStream_t stream);
 int enqueue_quantify(const CorrArgs<double>& A64, const int* d_rows, const int* d_cols, long long n, int inter,
                      double* d_score, double* d_nobs, FocusRec* d_rec, double* d_windows, hipStream_t stream);
+
+// CHROMOSIGHT_HIP_NO_FAST_WINDOWS=1: the wave-per-window kernels keep the general functions (rescore_pixel, lazy_gather_window)
+// where the compile-time-size ones above apply -- the two are the same sums in the same order
+inline bool fast_windows_on()
+{
+    return std::getenv("CHROMOSIGHT_HIP_NO_FAST_WINDOWS") == nullptr;     // (read per launch: the switch test flips it in-process)
+}
+
+// the pileup of the windows of n pixels (cs_pileup.hip, cs_pileup_blocks): records cut into consecutive chunks of pileup_chunk(n),
+// per chunk and pixel a sum and a count (d_part_sum / d_part_cnt: pileup_chunks(n) * km * kn entries each), then the chunks added
+// in chunk order into d_sum / d_cnt (km * kn entries each)
+constexpr long long kPileupMinChunk = 8;        // records of a chunk, at least
+constexpr long long kPileupMaxChunks = 512;     // chunks of a call, at most: the partials are a bounded scratch for any n
+inline long long pileup_chunk(long long n) { return std::max(kPileupMinChunk, (n + kPileupMaxChunks - 1) / kPileupMaxChunks); }
+inline long long pileup_chunks(long long n) { return n > 0 ? (n + pileup_chunk(n) - 1) / pileup_chunk(n) : 0; }
+int enqueue_pileup_batch(const CorrArgs<double>* d_tab, const int* d_inter, const int* d_blk, const int* d_rows, const int* d_cols,
+                         long long n, int kk, double* d_part_sum, long long* d_part_cnt, double* d_sum, long long* d_cnt,
+                         hipStream_t stream);
 
 // 1-D patterns of many sub-matrices in one launch chain (cs_foci.hip)
 constexpr long long kFociSmallMax = 1 << 16;       // candidates of one sub-matrix a single workgroup labels

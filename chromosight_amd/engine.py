@@ -516,6 +516,36 @@ def run_quantify_blocks(dev, blocks, kspec, blk, rows, cols, *, missing_tol=0.75
 
 
 @_one_call_per_context
+def run_pileup_blocks(dev, blocks, kshape, blk, rows, cols, stream=None):
+    """The pileup of the windows at positions of MANY staged sub-matrices, reduced on the device (cs_pileup_blocks): position t
+    is pixel (rows[t], cols[t]) of blocks[blk[t]], as in run_quantify_blocks; kshape = (km, kn).  Returns (sum (km, kn) float64,
+    cnt (km, kn) int64): per window pixel the sum of its non-NaN values over the positions and their number, summed in the fixed
+    order of include/chromosight_hip.h (bitwise reproducible)."""
+    blk = np.ascontiguousarray(blk, dtype=np.int32)
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    km, kn = int(kshape[0]), int(kshape[1])
+    # (the windows depend on the template's shape alone: any template of that shape names them)
+    kspec = KernelSpec(np.arange(km * kn, dtype=np.float64).reshape(km, kn))
+    k, n_blocks = rows.size, len(blocks)
+    sig_arr = (_lib.CsMatrix * n_blocks)(*[b.sig for b in blocks])
+    par_arr = (CsNormxcorr2Params * n_blocks)(*[
+        _corr_params(b.shape, kspec, True, not b.inter, b.max_dist, MASK_BINS, b.miss_row, b.miss_col, None, 0.75, CS_F64)
+        for b in blocks])
+    fp_arr = (CsFociParams * n_blocks)(*[CsFociParams(0.0, 0.0, 1, 0, 0, 0, int(bool(b.inter)), 0) for b in blocks])
+    total = np.empty((km, kn), dtype=np.float64)
+    count = np.empty((km, kn), dtype=np.int64)
+    dev._check(dev.lib.cs_pileup_blocks(dev.ctx, stream, n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr, blk.ctypes.data,
+                                        rows.ctypes.data, cols.ctypes.data, k, total.ctypes.data, count.ctypes.data))
+    return total, count
+
+
+def pileup_chunk(n):
+    """Positions per chunk of the pileup's summation order for n positions (cs_pileup_chunk; no GPU needed)."""
+    return int(_lib.load_library().cs_pileup_chunk(int(n)))
+
+
+@_one_call_per_context
 def run_compact(dev, corr, shape, threshold, lo_diag, hi_diag, stream=None, guess=1 << 16):
     """(rows, cols, vals) of the stored pixels of `corr` with value >= threshold inside the
     diagonal range; sorted row-major."""

@@ -695,6 +695,16 @@ def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False, smoo
     return results
 
 
+def _device_pileup(genome, staged, local, kernel_shape, dev=None, stream=None):
+    """(sum, count) over the windows of this rank's records `local` (GENOME_FIELDS rows: block, block-local bin1, bin2, ...) of
+    one template and iteration, from the staged blocks they were detected on (pipeline.pileup_blocks); zeros without records."""
+    if local.shape[0] == 0:
+        return np.zeros(kernel_shape), np.zeros(kernel_shape, dtype=np.int64)
+    from . import pipeline
+    ids, blk = np.unique(local[:, 0].astype(np.int64), return_inverse=True)
+    return pipeline.pileup_blocks(genome, [staged[int(ci)] for ci in ids], kernel_shape, blk, local[:, 1], local[:, 2], dev=dev, stream=stream)
+
+
 def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, stage=None, detect=None,
                   owned=None, staged=None, exchange=True, exclusive=True, own_context=False):
     """`chromosight detect` over all intra-chromosomal blocks of a DeviceCool, sharded over the ranks
@@ -760,6 +770,12 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
     # template's chain (labelling, statistics, the synchronisations) run under another's, and this thread applies the
     # acceptance rules (numpy, a third of a template's wall time on the 23-block genome) while the others are on the device.
     kernels = [np.asarray(k, dtype=np.float64) for k in kernel_config["kernels"]]
+    # An iterated template's pileup is reduced where its windows are (pipeline.pileup_blocks: the accepted records' pixels of the
+    # staged blocks, 2 km kn numbers back) when the device pipeline is in use: no iteration fetches windows then.
+    # CHROMOSIGHT_HIP_HOST_PILEUP=1 (and injected stage / detect): the windows of the non-final iterations are fetched and
+    # averaged on the host.
+    device_pileup = (batch is not None and stage_default and kernel_config["max_iterations"] > 1 and not pipeline.host_pileup())
+    pile_dev = pile_stream = None
     overlap = (batch is not None and stage_default and kernel_config["max_iterations"] == 1 and len(kernels) > 1 and bool(mine)
                and hasattr(genome, "workers") and not os.environ.get("CHROMOSIGHT_HIP_NO_TEMPLATE_OVERLAP"))
     futures = []
@@ -800,7 +816,7 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
         for it in range(kernel_config["max_iterations"]):
             rows, wins = [], []
             # the windows only feed the pileup of the next iteration: the last one does not fetch them
-            need_windows = it + 1 < kernel_config["max_iterations"]
+            need_windows = it + 1 < kernel_config["max_iterations"] and not device_pileup
             if joint is not None:
                 results = joint[kernel_id]
             elif overlap:
@@ -816,6 +832,7 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
                 else:
                     genome.dev.sync()
                 results = batch(genome, [staged[ci] for ci in mine], kernel_config, kernel, tsvd, need_windows, False, dev_t, stream_t)
+                pile_dev, pile_stream = dev_t, stream_t
             else:
                 results = batch(genome, [staged[ci] for ci in mine], kernel_config, kernel, tsvd, need_windows) if batch else None
             if isinstance(results, tuple):
@@ -856,17 +873,27 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
             # patterns (no pattern on any rank: next template, cli/chromosight.py:786-789); the records wait for the end
             if it + 1 == kernel_config["max_iterations"]:
                 continue                                     # nothing depends on the last iteration's patterns
-            stack = np.concatenate(wins, axis=0) if wins else np.zeros((0,) + kernel.shape)
-            if world == 1:
-                if local.shape[0] == 0:
-                    break
-                import warnings
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore")
-                    kernel = np.nanmean(stack, axis=0)           # detection.py:158-174
-                continue
-            both = np.concatenate([np.nansum(stack, axis=0).ravel(), np.sum(~np.isnan(stack), axis=0).astype(np.float64).ravel(),
-                                   [float(local.shape[0])]])
+            if device_pileup:
+                total, count = _device_pileup(genome, staged, local, kernel.shape, pile_dev, pile_stream)
+                if world == 1:
+                    if local.shape[0] == 0:
+                        break
+                    with np.errstate(all="ignore"):
+                        kernel = total / count                   # 0 / 0: NaN, as np.nanmean (detection.py:158-174)
+                    continue
+                both = np.concatenate([total.ravel(), count.astype(np.float64).ravel(), [float(local.shape[0])]])
+            else:
+                stack = np.concatenate(wins, axis=0) if wins else np.zeros((0,) + kernel.shape)
+                if world == 1:
+                    if local.shape[0] == 0:
+                        break
+                    import warnings
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")
+                        kernel = np.nanmean(stack, axis=0)           # detection.py:158-174
+                    continue
+                both = np.concatenate([np.nansum(stack, axis=0).ravel(), np.sum(~np.isnan(stack), axis=0).astype(np.float64).ravel(),
+                                       [float(local.shape[0])]])
             both = _allreduce_sum(both)
             if both[-1] == 0:
                 break

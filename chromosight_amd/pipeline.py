@@ -1182,6 +1182,26 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
     return done(cid.accept_many(blocks, rec, windows, counts, engine.KernelSpec(kernel, tsvd), kernel_config, pvals=True))
 
 
+def host_pileup():
+    """True with CHROMOSIGHT_HIP_HOST_PILEUP=1: an iterated template's pileup is formed on the host from fetched windows
+    (np.nanmean) instead of on the device (pileup_blocks)."""
+    return bool(os.environ.get("CHROMOSIGHT_HIP_HOST_PILEUP"))
+
+
+def pileup_blocks(dcool, blocks, kernel_shape, blk, rows, cols, dev=None, stream=None):
+    """Pileup of the windows of given pixels of staged blocks, reduced on the device (cs_pileup_blocks): position t is the
+    block-local pixel (rows[t], cols[t]) of blocks[blk[t]] -- the (bin1, bin2) of a detect record of that block.  Returns
+    (sum, cnt), (km, kn) arrays: per window pixel the sum of its non-NaN values over the positions (float64) and their number
+    (int64); sum / cnt is the template `detect --iterations` continues with (cid.pileup_patterns of the same windows, summed
+    in the fixed order of include/chromosight_hip.h instead of numpy's).  The windows are those of detect_blocks /
+    quantify: nothing but the two small arrays leaves the device."""
+    km, kn = (int(x) for x in kernel_shape)
+    big = np.iinfo(np.int32).max // 2
+    rows = np.clip(np.asarray(rows, dtype=np.int64), -big, big)
+    cols = np.clip(np.asarray(cols, dtype=np.int64), -big, big)
+    return engine.run_pileup_blocks(dev or dcool.dev, list(blocks), (km, kn), blk, rows, cols, stream=stream)
+
+
 def _strip_reach(kernels):
     """The template side whose halo a row strip of a trans block needs for these templates: (reach - 1) // 2 rows cover the
     windows of the rows it owns, plus |kh - kw| for a non-square template (in full mode its score is read kh - kw rows away:

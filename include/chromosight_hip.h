@@ -576,6 +576,24 @@ int cs_quantify_blocks(cs_ctx* ctx, void* stream, int32_t n_blocks, const cs_mat
                        const cs_normxcorr2_params* params, const cs_foci_params* foci, const int32_t* h_blk,
                        const int32_t* h_rows, const int32_t* h_cols, int64_t n, cs_focus* h_out, double* h_windows);
 
+/* The pileup of the windows at the same kind of pixel list, reduced on the device (`detect --iterations` replaces a template by
+ * the pixel-wise mean of the windows it detected, NaN ignored: cli/chromosight.py:732, 791; detection.py:158-174).  Arguments
+ * and checks as for cs_quantify_blocks (want_windows is not read); the float64 signals may also be the CS_LAYOUT_BAND_LAZY
+ * descriptors of the detection path (cs_stage_block), which evaluate to the values of the stored band.  Window pixel e of position t is exactly the value
+ * cs_quantify_blocks writes to h_windows[t * km * kn + e] (zeros of the frame, NaN on the sub-diagonals of intra maps, on
+ * undetectable rows and columns, everywhere when the window leaves the map).  h_sum[e]: the sum of the non-NaN values of pixel
+ * e over the n positions; h_cnt[e]: their number (km * kn entries each; n == 0: zeros, nothing is launched).  The caller forms
+ * h_sum / h_cnt (0 / 0: NaN, as np.nanmean gives).  Synchronous.
+ * ORDER OF THE SUMS -- fixed, so that the result is bitwise reproducible and a few lines of numpy restate it: the positions are
+ * cut into consecutive chunks of S = cs_pileup_chunk(n) (a function of n and compile-time constants only: max(8, ceil(n / 512)),
+ * so at most 512 chunks' partial sums and counts are held as scratch whatever n is).  Within a chunk a pixel is accumulated from
+ * +0.0 in position order; the chunks' partial sums are then added from +0.0 in chunk order.  No floating-point atomics, nothing
+ * depends on the launch grid or the device. */
+int cs_pileup_blocks(cs_ctx* ctx, void* stream, int32_t n_blocks, const cs_matrix* signals, const cs_kernel* kernel,
+                     const cs_normxcorr2_params* params, const cs_foci_params* foci, const int32_t* h_blk,
+                     const int32_t* h_rows, const int32_t* h_cols, int64_t n, double* h_sum, int64_t* h_cnt);
+int64_t cs_pileup_chunk(int64_t n);
+
 /* One sub-matrix split over several GPUs by row windows: pick_foci (detection.py:387-592)
  * needs the thresholded pixels of the whole map, so the two halves of cs_detect_foci are exposed.
  *
