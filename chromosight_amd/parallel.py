@@ -418,6 +418,17 @@ def _gather(records, n_fields, once=False):
     return merged[np.argsort(merged[:, 0], kind="stable")]
 
 
+def _own_blocks(genome, kernel_configs, owned=None):
+    """This rank's blocks: `owned` when the caller fixed the assignment, else longest-processing-time-first by the pixels scanned
+    at the longest keep distance of `kernel_configs`, the same lists on every rank."""
+    if owned is not None:
+        return list(owned)
+    dist, rank, world = _world()
+    max_dist = max(max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs)
+    costs = [block_cost((genome.chrom_size(ci),) * 2, max_dist, False) for ci in range(genome.n_chrom)]
+    return assign_blocks(costs, world)[rank]
+
+
 def stage_genome(genome, kernel_configs, owned=None, smooth=False, band_dtype=np.float64, lazy64=None):
     """Stage this rank's blocks for several pattern configurations (detect_genome(..., staged=...)): ONCE at the longest
     keep distance any of them needs, the others scan band views of the same blocks (DeviceCool.view_for).
@@ -425,7 +436,6 @@ def stage_genome(genome, kernel_configs, owned=None, smooth=False, band_dtype=np
     float64 bands are not stored beyond their first diagonals -- the exact evaluation of the candidates and the windows of
     the records recompute the pixels they read from the pixel table (pipeline.DeviceCool._stage_fast).
     Returns a StagedSet {chromosome: StagedBlock} (for_config(i): the set configuration i scans)."""
-    dist, rank, world = _world()
     if lazy64 is None:
         from .engine import get_precision
         lazy64 = (not os.environ.get("CHROMOSIGHT_HIP_F64_TWIN") and get_precision() == "f32"
@@ -433,11 +443,7 @@ def stage_genome(genome, kernel_configs, owned=None, smooth=False, band_dtype=np
                   and all(max(np.shape(k)) <= 17 for cfg in kernel_configs for k in cfg["kernels"]))
     dists = [max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs]
     tallest = [max(np.shape(k)[0] for k in cfg["kernels"]) for cfg in kernel_configs]
-    max_dist = max(dists)
-    if owned is None:
-        costs = [block_cost((genome.chrom_size(ci),) * 2, max_dist, False) for ci in range(genome.n_chrom)]
-        owned = assign_blocks(costs, world)[rank]
-    owned = list(owned)
+    owned = _own_blocks(genome, kernel_configs, owned)
     events = hasattr(genome, "dev") and hasattr(genome.dev, "new_event")
 
     def stage(which, slot):
@@ -610,12 +616,7 @@ def detect_patterns(genome, kernel_configs, owned=None, staged=None, tsvd=None, 
     global _PATTERN_THREADS
     if staged is None:
         staged = stage_genome(genome, kernel_configs, owned=owned, smooth=smooth)
-    dist, rank, world = _world()
-    if owned is None:
-        max_dist = max(max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs)
-        costs = [block_cost((genome.chrom_size(ci),) * 2, max_dist, False) for ci in range(genome.n_chrom)]
-        owned = assign_blocks(costs, world)[rank]
-    owned = list(owned)
+    owned = _own_blocks(genome, kernel_configs, owned)
     complete = all(ci in staged for ci in owned)
     side = [i for i, cfg in enumerate(kernel_configs) if cfg["max_iterations"] == 1] if complete and len(kernel_configs) > 1 else []
     if _PATTERN_THREADS is None and side:
@@ -661,12 +662,7 @@ def genome_step(genome, kernel_configs, owned=None, tsvd=None, local=False, smoo
         finally:
             _LOCAL_DEPTH[0] -= 1
     from . import plan as _plan
-    dist, rank, world = _world()
-    if owned is None:
-        max_dist = max(max(cfg["max_dist"] // genome.binsize, 1) for cfg in kernel_configs)
-        costs = [block_cost((genome.chrom_size(ci),) * 2, max_dist, False) for ci in range(genome.n_chrom)]
-        owned = assign_blocks(costs, world)[rank]
-    owned = list(owned)
+    owned = _own_blocks(genome, kernel_configs, owned)
     if not owned or not _plan.plannable(genome, kernel_configs, tsvd, smooth=smooth):
         staged = stage_genome(genome, kernel_configs, owned=owned, smooth=smooth)
         return detect_patterns(genome, kernel_configs, owned=owned, staged=staged, tsvd=tsvd, smooth=smooth)
@@ -705,14 +701,43 @@ def _device_pileup(genome, staged, local, kernel_shape, dev=None, stream=None):
     return pipeline.pileup_blocks(genome, [staged[int(ci)] for ci in ids], kernel_shape, blk, local[:, 1], local[:, 2], dev=dev, stream=stream)
 
 
+def _records(block_ids, table, kernel_id, iteration):
+    """GENOME_FIELDS rows of one template and iteration.  block_ids: one block's index (the table of that block) or one index per
+    row (a table merged over blocks); table: a (k, 4) array (bin1, bin2, score, pvalue) or a DataFrame with these columns."""
+    rec = np.empty((len(table), len(GENOME_FIELDS)))
+    rec[:, 0] = block_ids
+    rec[:, 1:5] = table if isinstance(table, np.ndarray) else table[["bin1", "bin2", "score", "pvalue"]].to_numpy(dtype=np.float64)
+    rec[:, 5] = kernel_id
+    rec[:, 6] = iteration
+    return rec
+
+
+def _refine(total, count, n_records):
+    """The template an iterated pattern continues with (cli/chromosight.py:791): the pileup sum / count over the windows of ALL
+    ranks, from this rank's (sum, count) per template pixel and its number of records -- or None when no rank found a pattern
+    (next template, cli/chromosight.py:786-789).  With several ranks ONE all-reduce carries the three together (2 km kn + 1
+    doubles).  0 / 0 is NaN, as in np.nanmean (detection.py:158-174)."""
+    both = _allreduce_sum(np.concatenate([np.ravel(total), np.ravel(count).astype(np.float64), [float(n_records)]]))
+    if both[-1] == 0:
+        return None
+    kk = np.size(total)
+    with np.errstate(all="ignore"):
+        return (both[:kk] / both[kk:2 * kk]).reshape(np.shape(total))
+
+
 def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.float64, stage=None, detect=None,
                   owned=None, staged=None, exchange=True, exclusive=True, own_context=False):
     """`chromosight detect` over all intra-chromosomal blocks of a DeviceCool, sharded over the ranks
     like the reference's Pool.imap over sub-matrices (cli/chromosight.py:738-755): every rank stages
-    and scans its own blocks (LPT assignment by band pixels), the per-block tables are all-gathered
-    (count + padded all_gather: RCCL over xGMI with the "nccl" backend), and when the template is
-    refined over iterations the pileup is formed from an all-reduce of the per-rank window sums and
-    counts, so every rank continues with the same template (cli/chromosight.py:791).
+    and scans its own blocks (LPT assignment by band pixels), the records of all templates and iterations
+    are all-gathered ONCE at the end (count + padded all_gather: RCCL over xGMI with the "nccl" backend),
+    and when the template is refined over iterations every non-final iteration ends with _refine: one all-reduce
+    of the per-rank pileup sums, counts and record numbers, so every rank continues with the same template.
+
+    How a template is scanned is chosen once, before the template x iteration loop: block by block through the
+    injected `stage` / `detect`; else -- the device pipeline -- the templates of a 1-D pattern in one launch chain on a
+    worker context (pipeline.detect_blocks_templates), several single-iteration templates side by side on worker
+    contexts, a template on this thread's own worker context (own_context), or the batched call on the genome's context.
 
     `genome` needs n_chrom, chrom_size(ci), binsize; `stage(genome, ci, max_dist, largest)` and
     `detect(genome, block, cfg, kernel, tsvd)` default to the device pipeline (injected in CPU tests).
@@ -725,26 +750,18 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
     (detect_patterns): every device call goes to a context and stream of this thread (a context serves one call in flight).
     Returns float64 records (block, bin1, bin2, score, pvalue, kernel_id, iteration), block-local
     bins, identical on all ranks, in the single-process order."""
-    batch = None
-    stage_default = stage is None
-    if stage is None and detect is None:
-        from . import pipeline
-        batch = lambda g, blks, cfg, k, t, w=True, defer=False, dev=None, stream=None: pipeline.detect_blocks(
-            g, blks, cfg, k, tsvd=t, raw=True, want_windows=w, defer=defer, dev=dev, stream=stream, merged=True,
-            exclusive=exclusive and len(kernel_config["kernels"]) == 1)
+    device_route = stage is None and detect is None          # the device pipeline stages and scans: nothing is injected
     if stage is None or detect is None:
         from . import pipeline
         stage = stage or (lambda g, ci, md, lk: g.stage_intra(ci, md, lk, smooth=smooth, band_dtype=band_dtype,
                                                               resident=True))
         detect = detect or (lambda g, blk, cfg, k, t: pipeline.detect_block(g, blk, cfg, k, tsvd=t, raw=True))
-    dist, rank, world = _world()
+    kernels = [np.asarray(k, dtype=np.float64) for k in kernel_config["kernels"]]
+    n_iter = kernel_config["max_iterations"]
     max_dist = max(kernel_config["max_dist"] // genome.binsize, 1)
-    largest = max(np.shape(k)[0] for k in kernel_config["kernels"])
-    sizes = [genome.chrom_size(ci) for ci in range(genome.n_chrom)]
-    costs = [block_cost((n, n), max_dist, False) for n in sizes]
-    mine = list(owned) if owned is not None else assign_blocks(costs, world)[rank]
+    largest = max(np.shape(k)[0] for k in kernels)
+    mine = _own_blocks(genome, [kernel_config], owned)
     have = {}
-    staged_in = staged
     if staged is not None:
         for ci in mine:
             blk = staged.get(ci)
@@ -757,153 +774,111 @@ def detect_genome(genome, kernel_config, tsvd=None, smooth=False, band_dtype=np.
             if view is not None:
                 have[ci] = view
     todo = [ci for ci in mine if ci not in have]
-    if batch is not None and stage_default:
+    # the event of the caller's staging; it does not cover blocks staged here
+    ready = getattr(staged, "ready", None) if not todo else None
+    if device_route:
         # the device pipeline stages its blocks with one native call (pipeline.DeviceCool.stage_blocks)
         fresh = dict(zip(todo, genome.stage_blocks(todo, max_dist, largest, smooth=smooth, band_dtype=band_dtype))) if todo else {}
     else:
         fresh = {ci: stage(genome, ci, max_dist, largest) for ci in todo}
     staged = {**have, **fresh}
-    out = []
-    pending = []
-    # Templates that do not depend on each other (a single iteration each) are scanned concurrently: one host thread per
-    # template, each with its own context and stream on this GPU (pipeline._Workers), so the latency-bound stages of one
-    # template's chain (labelling, statistics, the synchronisations) run under another's, and this thread applies the
-    # acceptance rules (numpy, a third of a template's wall time on the 23-block genome) while the others are on the device.
-    kernels = [np.asarray(k, dtype=np.float64) for k in kernel_config["kernels"]]
-    # An iterated template's pileup is reduced where its windows are (pipeline.pileup_blocks: the accepted records' pixels of the
-    # staged blocks, 2 km kn numbers back) when the device pipeline is in use: no iteration fetches windows then.
-    # CHROMOSIGHT_HIP_HOST_PILEUP=1 (and injected stage / detect): the windows of the non-final iterations are fetched and
-    # averaged on the host.
-    device_pileup = (batch is not None and stage_default and kernel_config["max_iterations"] > 1 and not pipeline.host_pileup())
-    pile_dev = pile_stream = None
-    overlap = (batch is not None and stage_default and kernel_config["max_iterations"] == 1 and len(kernels) > 1 and bool(mine)
-               and hasattr(genome, "workers") and not os.environ.get("CHROMOSIGHT_HIP_NO_TEMPLATE_OVERLAP"))
-    futures = []
-    joint = None
-    # (a 1-D pattern with ONE template -- hairpins -- takes the same joint chain: the entry serves 1 to 4 templates, and it is the
-    # chain a StepPlan replays, chromosight_amd/plan.py)
-    one_template_1d = (batch is not None and stage_default and kernel_config["max_iterations"] == 1 and len(kernels) == 1 and bool(mine)
-                       and hasattr(genome, "workers") and not os.environ.get("CHROMOSIGHT_HIP_NO_TEMPLATE_OVERLAP"))
-    if (overlap or one_template_1d) and kernel_config["max_dist"] == 0 and tsvd is None and not todo:
-        # a 1-D pattern's templates share one launch chain (cs_detect_foci_batch_templates): on a worker context, so that the
-        # chain runs beside whatever this genome's own stream is doing (another pattern's tile kernels)
-        pool = genome.workers(1)
-        ready = getattr(staged_in, "ready", None)
+    blocks = [staged[ci] for ci in mine]
+
+    def batch(kernel, want_windows, defer=False, dev=None, stream=None):
+        return pipeline.detect_blocks(genome, blocks, kernel_config, kernel, tsvd=tsvd, raw=True, want_windows=want_windows, defer=defer,
+                                      dev=dev, stream=stream, merged=True, exclusive=exclusive and len(kernels) == 1)
+
+    def after_staging(pool):
+        """On the calling thread: the host waits for the genome's stream when no event says that the staged blocks are complete.
+        Returns a callable for a thread of `pool`: its (dev, stream), the stream behind that event."""
         if ready is None:
             genome.dev.sync()
-        dev, stream = pool.device()
-        if ready is not None:
-            dev.wait_event(ready, stream)
-        joint = pipeline.detect_blocks_templates(genome, [staged[ci] for ci in mine], kernel_config, kernels, dev=dev, stream=stream)
-        if joint is not None:
-            joint = joint()                                  # the acceptance rules, here
-            overlap = False
-    if overlap:
-        pool = genome.workers(min(len(kernels), 3))
-        ready = getattr(staged_in, "ready", None) if not todo else None
-        if ready is None:
-            genome.dev.sync()                                # the staged blocks are complete before other streams read them
-        blocks_mine = [staged[ci] for ci in mine]
 
-        def scan(k):
+        def take():
             dev, stream = pool.device()
             if ready is not None:
                 dev.wait_event(ready, stream)                # device-side: the staging of these blocks has finished
-            return batch(genome, blocks_mine, kernel_config, kernels[k], tsvd, False, True, dev, stream)
+            return dev, stream
 
-        futures = [pool.pool.submit(scan, k) for k in range(len(kernels))]
+        return take
+
+    def parts_of(results):
+        """What a scan found as ([(block ids, table)], [windows]), from the merged triple of a batch entry (the table of all
+        blocks, the records per block, windows or None) or from one (table, windows) per block."""
+        if isinstance(results, tuple):
+            table, kept, windows = results
+            return [(np.repeat(np.asarray(mine, dtype=np.float64), kept), table)], [] if windows is None else [windows]
+        found = [(ci, table, windows) for ci, (table, windows) in zip(mine, results) if table is not None and len(table)]
+        return [(ci, table) for ci, table, _ in found], [windows for _, _, windows in found if windows is not None]
+
+    # scan(kernel_id, kernel, need_windows): this rank's parts_of for one template.  The route is chosen here, once.
+    # Templates that do not depend on each other (a single iteration each) are scanned concurrently when the genome has worker
+    # contexts (pipeline._Workers); CHROMOSIGHT_HIP_NO_TEMPLATE_OVERLAP=1 scans them in turn.
+    side_by_side = (device_route and n_iter == 1 and bool(mine) and hasattr(genome, "workers")
+                    and not os.environ.get("CHROMOSIGHT_HIP_NO_TEMPLATE_OVERLAP"))
+    pile_on = (None, None)                                   # where the device pileup runs: the genome's context and stream
+    joint = None
+    if side_by_side and kernel_config["max_dist"] == 0 and tsvd is None and not todo:
+        # a 1-D pattern's templates share one launch chain (cs_detect_foci_batch_templates): on a worker context, so that the
+        # chain runs beside whatever this genome's own stream is doing (another pattern's tile kernels).  ONE template --
+        # hairpins -- takes it too: the entry serves 1 to 4 templates, and it is the chain a StepPlan replays (plan.py)
+        dev, stream = after_staging(genome.workers(1))()
+        joint = pipeline.detect_blocks_templates(genome, blocks, kernel_config, kernels, dev=dev, stream=stream)
+    if not device_route:
+        scan = lambda kernel_id, kernel, need_windows: parts_of([detect(genome, staged[ci], kernel_config, kernel, tsvd) for ci in mine])
+    elif joint is not None:
+        joint = joint()                                      # the acceptance rules, here
+        scan = lambda kernel_id, kernel, need_windows: parts_of(joint[kernel_id])
+    elif side_by_side and len(kernels) > 1:
+        # one host thread per template, each with its own context and stream on this GPU, so the latency-bound stages of one
+        # template's chain (labelling, statistics, the synchronisations) run under another's.  The acceptance rules (many small
+        # numpy calls) run in scan, on this thread, one template after the other while the others are on the device: spread
+        # over the worker threads they fight for the interpreter lock and each takes four times as long
+        pool = genome.workers(min(len(kernels), 3))
+        take = after_staging(pool)
+
+        def chain(kernel):
+            dev, stream = take()
+            return batch(kernel, False, True, dev, stream)
+
+        futures = [pool.pool.submit(chain, kernel) for kernel in kernels]
+        scan = lambda kernel_id, kernel, need_windows: parts_of(futures[kernel_id].result()())
+    elif own_context and hasattr(genome, "workers"):
+        # on a pool thread: not on the genome's context, which the calling thread is using
+        pool = genome.workers(1)
+        pile_on = pool.device()
+
+        def scan(kernel_id, kernel, need_windows):
+            dev, stream = after_staging(pool)()              # (before every call: each one reads the staged blocks)
+            return parts_of(batch(kernel, need_windows, False, dev, stream))
+    else:
+        scan = lambda kernel_id, kernel, need_windows: parts_of(batch(kernel, need_windows))
+    # An iterated template's pileup is reduced where its windows are (pipeline.pileup_blocks: the accepted records' pixels of the
+    # staged blocks, 2 km kn numbers back) when the device pipeline is in use: no iteration fetches windows then.
+    # CHROMOSIGHT_HIP_HOST_PILEUP=1 (and injected stage / detect): the windows of the non-final iterations are fetched and
+    # summed on the host.
+    device_pileup = device_route and n_iter > 1 and not pipeline.host_pileup()
+    pending = []                                             # gathered once, at the end of the call
     for kernel_id, kernel in enumerate(kernels):
-        for it in range(kernel_config["max_iterations"]):
-            rows, wins = [], []
-            # the windows only feed the pileup of the next iteration: the last one does not fetch them
-            need_windows = it + 1 < kernel_config["max_iterations"] and not device_pileup
-            if joint is not None:
-                results = joint[kernel_id]
-            elif overlap:
-                # the acceptance rules (many small numpy calls) here, one template after the other: spread over the worker
-                # threads they fight for the interpreter lock and each takes four times as long
-                results = futures[kernel_id].result()()
-            elif batch and own_context and hasattr(genome, "workers"):
-                # a single template on a pool thread: not on the genome's context, which the calling thread is using
-                dev_t, stream_t = genome.workers(1).device()
-                ready_t = getattr(staged_in, "ready", None) if not todo else None
-                if ready_t is not None:
-                    dev_t.wait_event(ready_t, stream_t)
-                else:
-                    genome.dev.sync()
-                results = batch(genome, [staged[ci] for ci in mine], kernel_config, kernel, tsvd, need_windows, False, dev_t, stream_t)
-                pile_dev, pile_stream = dev_t, stream_t
-            else:
-                results = batch(genome, [staged[ci] for ci in mine], kernel_config, kernel, tsvd, need_windows) if batch else None
-            if isinstance(results, tuple):
-                # one native call covered every block: its table is already the concatenation of the blocks' tables
-                table, kept, windows = results
-                rec = np.empty((len(table), len(GENOME_FIELDS)))
-                rec[:, 0] = np.repeat(np.asarray(mine, dtype=np.float64), kept)
-                rec[:, 1:5] = table
-                rec[:, 5] = kernel_id
-                rec[:, 6] = it
-                rows.append(rec)
-                if windows is not None:
-                    wins.append(windows)
-            for pos, ci in enumerate(mine if not isinstance(results, tuple) else ()):
-                table, windows = results[pos] if results is not None else detect(genome, staged[ci], kernel_config,
-                                                                                kernel, tsvd)
-                if table is None or len(table) == 0:
-                    continue
-                rec = np.empty((len(table), len(GENOME_FIELDS)))
-                rec[:, 0] = ci
-                if isinstance(table, np.ndarray):              # raw records (bin1, bin2, score, pvalue)
-                    rec[:, 1:5] = table
-                else:
-                    rec[:, 1] = table["bin1"].to_numpy(dtype=np.float64)
-                    rec[:, 2] = table["bin2"].to_numpy(dtype=np.float64)
-                    rec[:, 3] = table["score"].to_numpy(dtype=np.float64)
-                    rec[:, 4] = table["pvalue"].to_numpy(dtype=np.float64)
-                rec[:, 5] = kernel_id
-                rec[:, 6] = it
-                rows.append(rec)
-                if windows is not None:
-                    wins.append(windows)
-            local = np.concatenate(rows, axis=0) if rows else np.zeros((0, len(GENOME_FIELDS)))
-            pending.append(local)                            # gathered once, at the end of the call
-            if kernel_config["max_iterations"] == 1:
-                continue
-            # iterated template: ONE all-reduce per iteration carries the pileup sums, their counts and the number of
-            # patterns (no pattern on any rank: next template, cli/chromosight.py:786-789); the records wait for the end
-            if it + 1 == kernel_config["max_iterations"]:
-                continue                                     # nothing depends on the last iteration's patterns
+        for it in range(n_iter):
+            last = it + 1 == n_iter
+            parts, wins = scan(kernel_id, kernel, not last and not device_pileup)
+            local = np.concatenate([_records(ids, table, kernel_id, it) for ids, table in parts] or [np.zeros((0, len(GENOME_FIELDS)))])
+            pending.append(local)
+            if last:
+                break                                        # nothing depends on the last iteration's patterns: no windows, no reduction
             if device_pileup:
-                total, count = _device_pileup(genome, staged, local, kernel.shape, pile_dev, pile_stream)
-                if world == 1:
-                    if local.shape[0] == 0:
-                        break
-                    with np.errstate(all="ignore"):
-                        kernel = total / count                   # 0 / 0: NaN, as np.nanmean (detection.py:158-174)
-                    continue
-                both = np.concatenate([total.ravel(), count.astype(np.float64).ravel(), [float(local.shape[0])]])
+                total, count = _device_pileup(genome, staged, local, kernel.shape, *pile_on)
             else:
                 stack = np.concatenate(wins, axis=0) if wins else np.zeros((0,) + kernel.shape)
-                if world == 1:
-                    if local.shape[0] == 0:
-                        break
-                    import warnings
-                    with warnings.catch_warnings():
-                        warnings.simplefilter("ignore")
-                        kernel = np.nanmean(stack, axis=0)           # detection.py:158-174
-                    continue
-                both = np.concatenate([np.nansum(stack, axis=0).ravel(), np.sum(~np.isnan(stack), axis=0).astype(np.float64).ravel(),
-                                       [float(local.shape[0])]])
-            both = _allreduce_sum(both)
-            if both[-1] == 0:
+                total, count = np.nansum(stack, axis=0), np.sum(~np.isnan(stack), axis=0)
+            kernel = _refine(total, count, local.shape[0])
+            if kernel is None:
                 break
-            kk = kernel.size
-            with np.errstate(all="ignore"):
-                kernel = (both[:kk] / both[kk:2 * kk]).reshape(kernel.shape)
     local = np.concatenate(pending, axis=0) if pending else np.zeros((0, len(GENOME_FIELDS)))
     if not exchange:
         return local                                         # detect_patterns: the caller exchanges (in a fixed order)
-    return _exchange_records(local, len(kernels), kernel_config["max_iterations"])
+    return _exchange_records(local, len(kernels), n_iter)
 
 
 # ================================================================================================

@@ -1111,20 +1111,29 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
     if any(min(b.shape) > max(kernel.shape) for b in blocks):
         _check_template(kernel)
     square = kernel.shape[0] == kernel.shape[1]
-    if len(blocks) > 1 and raw and batch and square and tsvd is None:
+    one_d = kernel_config["max_dist"] == 0
+    plain = raw and tsvd is None                             # the batch entries' own raw tables: deferred, merged on request
+    if len(blocks) > 1 and batch and square and (plain or one_d):
         live = [k for k, b in enumerate(blocks) if min(b.shape) > max(kernel.shape)]
         banded = [k for k in live if blocks[k].is_band]
         kspec = engine.KernelSpec(kernel, tsvd)
         fin = None
-        if len(banded) > 1:
-            many = cid.detect_many_on_device if kernel_config["max_dist"] == 0 else cid.detect_blocks_on_device
-            extra = dict(raw=True) if kernel_config["max_dist"] == 0 else dict(exclusive=exclusive)
+        if len(banded) > 1 and plain:
+            many = cid.detect_many_on_device if one_d else cid.detect_blocks_on_device
+            extra = dict(raw=True) if one_d else dict(exclusive=exclusive)
             whole = merged and len(banded) == len(blocks)
             fin = many(bdev, [blocks[k] for k in banded], kspec, kernel_config, want_windows=want_windows, defer=True, stream=stream,
                        merged=whole, **extra)
             if fin is not None and whole:
                 return fin if defer else fin()
+        elif len(banded) > 1:
+            # a truncated-SVD template, or tables as DataFrames (1-D patterns only): the same batch, accepted block by block in
+            # the call (on the caller's context and stream: several host threads may be scanning templates side by side)
+            res = cid.detect_many_on_device(bdev, [blocks[k] for k in banded], kspec, kernel_config, raw=raw, want_windows=want_windows,
+                                            stream=stream)
+            fin = None if res is None else (lambda: res)
         if fin is not None:
+            # what the library cannot batch goes block by block
             rest = {k: detect_block(dcool, blocks[k], kernel_config, kernel, tsvd=tsvd, raw=raw, want_windows=want_windows, dev=dev,
                                     stream=stream)
                     for k in live if k not in banded}
@@ -1138,22 +1147,6 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
                 return out
 
             return finish if defer else finish()
-    elif len(blocks) > 1 and kernel_config["max_dist"] == 0 and batch and square:
-        # 1-D patterns, tables as DataFrames: the same batch, accepted block by block
-        live = [k for k, b in enumerate(blocks) if min(b.shape) > max(kernel.shape)]
-        banded = [k for k in live if blocks[k].is_band]
-        # (on the caller's context and stream: several host threads may be scanning templates side by side)
-        res = cid.detect_many_on_device(bdev, [blocks[k] for k in banded], engine.KernelSpec(kernel, tsvd), kernel_config,
-                                        raw=raw, want_windows=want_windows, stream=stream) if len(banded) > 1 else None
-        if res is not None:
-            out = [(None, None)] * len(blocks)
-            for k, r in zip(banded, res):
-                out[k] = r
-            for k in live:
-                if k not in banded:
-                    out[k] = detect_block(dcool, blocks[k], kernel_config, kernel, tsvd=tsvd, raw=raw, want_windows=want_windows,
-                                          dev=dev, stream=stream)
-            return done(out)
     if workers <= 1 or len(blocks) <= 1 or dev is not None:
         # (a caller that brought its own context and stream -- a template scanned beside others -- keeps every call on them:
         # that stream is the one that waited for the staging of the blocks)
@@ -1184,7 +1177,7 @@ def detect_blocks(dcool, blocks, kernel_config, kernel, tsvd=None, raw=True, wor
 
 def host_pileup():
     """True with CHROMOSIGHT_HIP_HOST_PILEUP=1: an iterated template's pileup is formed on the host from fetched windows
-    (np.nanmean) instead of on the device (pileup_blocks)."""
+    (np.nansum over their count: np.nanmean) instead of on the device (pileup_blocks)."""
     return bool(os.environ.get("CHROMOSIGHT_HIP_HOST_PILEUP"))
 
 

@@ -185,6 +185,131 @@ def test_detect_genome_world2_equals_single(tmp_path):
         assert np.array_equal(np.load(tmp_path / f"genome_one{r}.npy"), single_one)      # same rows, same order
 
 
+def test_records_from_arrays_and_frames():
+    """parallel._records: the same four columns as a (k, 4) array and as a DataFrame, for one block and for a block per row."""
+    import pandas as pd
+    rng = np.random.default_rng(3)
+    table = np.column_stack([rng.integers(0, 90, 6), rng.integers(0, 90, 6), rng.random(6), rng.random(6)])
+    frame = pd.DataFrame({"bin1": table[:, 0].astype(np.int64), "bin2": table[:, 1].astype(np.int64), "score": table[:, 2],
+                          "pvalue": table[:, 3], "kernel_id": 9})                 # (ignores columns of its own)
+    ids = np.repeat([2, 5, 11], [1, 3, 2])
+    for block_ids, first in ((4, np.full(6, 4.0)), (ids, ids.astype(np.float64))):
+        want = np.column_stack([first, table, np.full(6, 1.0), np.full(6, 2.0)])
+        for given in (table, frame):
+            got = parallel._records(block_ids, given, 1, 2)
+            assert got.dtype == np.float64 and got.shape == (6, len(parallel.GENOME_FIELDS))
+            assert np.array_equal(got, want)
+    assert parallel._records(ids[:0], table[:0], 0, 0).shape == (0, len(parallel.GENOME_FIELDS))
+
+
+class _Genome4(_Genome):
+    n_chrom = 4
+
+
+def _sure_detect(genome, block, cfg, kernel, tsvd):
+    """_fake_detect that always finds something: 1 + ci patterns, keyed on the block and on the template."""
+    import pandas as pd
+    n = 1 + block["ci"]
+    rng = np.random.default_rng(block["ci"] * 1000 + int(round(float(np.nansum(kernel)) * 1e6)) % 997)
+    wins = rng.random((n, 3, 3))
+    wins[rng.random((n, 3, 3)) < 0.2] = np.nan
+    return pd.DataFrame({"bin1": rng.integers(0, block["n"], n), "bin2": rng.integers(0, block["n"], n),
+                         "score": rng.random(n), "pvalue": rng.random(n)}), wins
+
+
+_SEEN = []          # (block, template) of every call the stand-ins below receive, per process
+
+
+def _detect_nothing_for_the_first_template(genome, block, cfg, kernel, tsvd):
+    _SEEN.append((block["ci"], np.array(kernel)))
+    if np.array_equal(kernel, _CFG["kernels"][0]):
+        return None, None
+    return _sure_detect(genome, block, cfg, kernel, tsvd)
+
+
+def _detect_in_blocks_0_and_1(genome, block, cfg, kernel, tsvd):
+    _SEEN.append((block["ci"], np.array(kernel)))
+    if block["ci"] >= 2:
+        return None, None
+    return _sure_detect(genome, block, cfg, kernel, tsvd)
+
+
+def _seen(path=None):
+    """The calls recorded in _SEEN (emptied): block indices and templates, optionally saved."""
+    blocks, templates = np.array([ci for ci, _ in _SEEN]), np.array([k for _, k in _SEEN]).reshape(-1, 3, 3)
+    _SEEN.clear()
+    if path is not None:
+        np.savez(path, blocks=blocks, templates=templates)
+    return blocks, templates
+
+
+def _refine_worker(rank, world, port, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        got = parallel.detect_genome(_Genome(), _CFG, stage=_fake_stage, detect=_detect_nothing_for_the_first_template)
+        np.save(os.path.join(out_dir, f"nothing{rank}.npy"), got)
+        _seen(os.path.join(out_dir, f"nothing_seen{rank}.npz"))
+        got = parallel.detect_genome(_Genome4(), _CFG, stage=_fake_stage, detect=_detect_in_blocks_0_and_1, owned=[[0, 1], [2, 3]][rank])
+        np.save(os.path.join(out_dir, f"idle{rank}.npy"), got)
+        _seen(os.path.join(out_dir, f"idle_seen{rank}.npz"))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def refine_world2(tmp_path_factory):
+    out = tmp_path_factory.mktemp("refine_world2")
+    mp.spawn(_refine_worker, args=(2, _free_port(), str(out)), nprocs=2, join=True)
+    return out
+
+
+def test_no_pattern_anywhere_ends_a_templates_iterations(refine_world2):
+    """A template for which no rank finds a pattern in an iteration is not iterated further (cli/chromosight.py:786-789): no rows,
+    no more scans; the next template is scanned and iterated as usual.  One process and both of two ranks alike."""
+    n_iter, first = _CFG["max_iterations"], _CFG["kernels"][0]
+    single = parallel.detect_genome(_Genome(), _CFG, stage=_fake_stage, detect=_detect_nothing_for_the_first_template)
+    blocks, templates = _seen()
+    flat = np.array([np.array_equal(k, first) for k in templates])
+    # template 0: every block once; template 1: every block in every iteration
+    assert sorted(blocks[flat]) == list(range(_Genome.n_chrom))
+    assert sorted(blocks[~flat]) == sorted(list(range(_Genome.n_chrom)) * n_iter)
+    assert not (single[:, 5] == 0).any() and set(single[:, 6]) == set(range(n_iter))
+    assert single.shape[0] == n_iter * sum(1 + ci for ci in range(_Genome.n_chrom))
+    scanned = []
+    for r in range(2):
+        assert np.array_equal(np.load(refine_world2 / f"nothing{r}.npy"), single)
+        seen = np.load(refine_world2 / f"nothing_seen{r}.npz")
+        flat = np.array([np.array_equal(k, first) for k in seen["templates"]])
+        own = sorted(seen["blocks"][flat])
+        assert len(own) == len(set(own)) and sorted(seen["blocks"][~flat]) == sorted(own * n_iter)
+        scanned += own
+    assert sorted(scanned) == list(range(_Genome.n_chrom))
+
+
+def test_a_rank_without_records_goes_on_iterating(refine_world2):
+    """Patterns only in the blocks of rank 0: rank 1 finds nothing in any iteration, and still scans every iteration with the
+    template all ranks continue with -- the all-reduced pileup, not its own empty one."""
+    n_iter, n_k = _CFG["max_iterations"], len(_CFG["kernels"])
+    single = parallel.detect_genome(_Genome4(), _CFG, stage=_fake_stage, detect=_detect_in_blocks_0_and_1, owned=[0, 1, 2, 3])
+    blocks, templates = _seen()
+    assert blocks.tolist() == [0, 1, 2, 3] * (n_k * n_iter)
+    assert single.shape[0] == n_k * n_iter * 3 and set(single[:, 0]) == {0.0, 1.0} and set(single[:, 6]) == set(range(n_iter))
+    seen = [np.load(refine_world2 / f"idle_seen{r}.npz") for r in range(2)]
+    for r, own in enumerate(([0, 1], [2, 3])):
+        assert seen[r]["blocks"].tolist() == own * (n_k * n_iter)
+        got = np.load(refine_world2 / f"idle{r}.npy")
+        assert got.shape == single.shape
+        assert np.array_equal(got[:, [0, 1, 2, 5, 6]], single[:, [0, 1, 2, 5, 6]])
+        assert np.allclose(got[:, 3:5], single[:, 3:5], rtol=0, atol=1e-12)
+    # scan by scan both ranks hold the same template, which is the single process's up to the rounding of the sum over ranks
+    assert np.array_equal(seen[0]["templates"], seen[1]["templates"], equal_nan=True)
+    assert np.allclose(seen[1]["templates"][::2], templates[::4], rtol=1e-13, atol=0, equal_nan=True)
+    refined = seen[1]["templates"][2]                          # rank 1, template 0, iteration 1
+    assert not np.array_equal(refined, _CFG["kernels"][0]) and np.isfinite(refined).any()
+
+
 # ------------------------------------------------------------------------------------------------
 # quantify: sub-matrices dealt to the ranks, one exchange of scores and windows (QuantifyShard)
 # ------------------------------------------------------------------------------------------------
