@@ -1205,15 +1205,9 @@ int build_args(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const c
     A.w_lr2 = tc.lr2;
     A.w_lrc = tc.lra;
     A.w_lrb = tc.lrb;
-    A.row_begin = 0;
-    A.row_end = p->ms;
-    if (p->row_end > p->row_begin) {
-        if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
-        if ((p->row_begin != 0 || p->row_end != p->ms) && p->mask_mode == CS_MASK_EXPLICIT)
-            return fail(ctx, CS_ERR_UNSUPPORTED, "row windows need per-bin masks or none");
-        A.row_begin = p->row_begin;
-        A.row_end = p->row_end;
-    }
+    if (int rc_win = row_window_of(ctx, p, &A.row_begin, &A.row_end)) return rc_win;
+    if ((A.row_begin != 0 || A.row_end != p->ms) && p->mask_mode == CS_MASK_EXPLICIT)
+        return fail(ctx, CS_ERR_UNSUPPORTED, "row windows need per-bin masks or none");
     *out = A;
     return CS_OK;
 }

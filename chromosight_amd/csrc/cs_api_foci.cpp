@@ -24,6 +24,74 @@ static int check_foci_args(cs_ctx* ctx, const cs_matrix* signal, const cs_kernel
 }
 
 namespace {
+// The layout of a call's scratch (ctx->d_pool): 256-byte-aligned pieces, handed out in order.
+struct Carve {
+    size_t at = 0;
+    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+    size_t take(size_t bytes) { const size_t off = at; at += al(bytes); return off; }
+    size_t total() const { return at; }
+};
+
+// (the helpers are static: inside extern "C" an unnamed namespace does not keep a function out of the library's symbol table)
+// The device pointer of a page-locked host pointer (what cs_host_alloc hands out), or null.
+static void* device_view(const void* h)
+{
+    if (!h) return nullptr;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, h) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
+}
+
+// The device views of an entry's record and window buffers; false when a buffer it has to fill is not page-locked.
+static bool pinned_views(cs_focus* h_foci, int64_t cap, bool want_windows, double* h_windows, cs::FocusRec** rec, double** win)
+{
+    *rec = cap > 0 ? reinterpret_cast<cs::FocusRec*>(device_view(h_foci)) : nullptr;
+    *win = (want_windows && h_windows) ? reinterpret_cast<double*>(device_view(h_windows)) : nullptr;
+    return !(cap > 0 && !*rec) && !(want_windows && h_windows && !*win);
+}
+
+// ... of a batched entry: results straight into page-locked caller buffers (cs_host_alloc), nothing else
+static int batch_views(cs_ctx* ctx, cs_focus* h_foci, int64_t cap, bool want_windows, double* h_windows, cs::FocusRec** rec, double** win)
+{
+    if (pinned_views(h_foci, cap, want_windows, h_windows, rec, win)) return CS_OK;
+    return fail(ctx, CS_ERR_UNSUPPORTED, "the batch entry writes into page-locked buffers (cs_host_alloc)");
+}
+
+// per-block counts of a batched entry (the total + n of them + a spare) through a page-locked array owned by the context
+static int ensure_blk_counts(cs_ctx* ctx, size_t n)
+{
+    const size_t cnt_bytes = 8 * (n + 2);
+    if (cnt_bytes <= ctx->h_blk_bytes) return CS_OK;
+    if (ctx->h_blk_counts) CS_HIP(ctx, hipHostFree(ctx->h_blk_counts));
+    ctx->h_blk_counts = nullptr;
+    ctx->h_blk_bytes = 0;
+    CS_HIP(ctx, hipHostMalloc((void**)&ctx->h_blk_counts, 2 * cnt_bytes, hipHostMallocDefault));
+    ctx->h_blk_bytes = 2 * cnt_bytes;
+    return CS_OK;
+}
+
+// a band with storage of its own (not lazily evaluated, not raw counts): what the single-block entries scan as a band
+inline bool stored_band(int layout) { return layout == CS_LAYOUT_BAND || layout == CS_LAYOUT_BAND_PADDED; }
+
+// The geometry (no storage) of a scan's coefficient map from row0 on: the scanned diagonals of a band, else ns columns.
+static cs_matrix scan_map(int layout, int dtype, int ns, int lo_diag, int hi_diag, int row0)
+{
+    const int w = hi_diag - lo_diag + 1;
+    if (is_band(layout)) return cs_matrix{nullptr, dtype, CS_LAYOUT_BAND, ((int64_t)w + 63) / 64 * 64, lo_diag, w, row0};
+    return cs_matrix{nullptr, dtype, layout, ((int64_t)ns + 15) / 16 * 16, 0, 0, row0};
+}
+
+// The first room for the candidates of a scan of `pixels` pixels (a list that outgrows it sends its call round again).  kHeads: room
+// of the host block of cs_candidates' one-synchronisation flow, which re-scores that many keys at most BEFORE the host has compared
+// the count with the room: they lie inside any first room.
+constexpr size_t kFirstRoom = 1 << 16;
+constexpr long long kHeads = 32768;
+static_assert((size_t)kHeads < kFirstRoom, "the one-synchronisation flow of cs_candidates reads up to kHeads keys of a first room");
+static size_t first_cand_room(size_t pixels) { return std::max<size_t>(kFirstRoom, pixels / 256); }
+
 // Where the masked matrix-core tile kernel appends its candidates (keys tag + row * ns + col); see CorrArgs::cand_keys.
 struct CandSink {
     unsigned long long* keys;
@@ -33,6 +101,8 @@ struct CandSink {
     int lo_diag, hi_diag;            // scanned diagonals
     void* defer_args = nullptr;      // see CorrArgs::defer_args: prepare the tile kernel's launch, do not launch
     int* defer_rsym = nullptr;
+    const int* tiles = nullptr;      // cs_candidates_tiles: the device list of the n_tiles tiles to visit (CorrArgs::cand_tiles)
+    int n_tiles = 0;
 };
 
 // float32 correlation in candidate mode (cs_device.h cand_screen_*: margin + conditioning screen, sentinel 2.0).  With a
@@ -59,8 +129,8 @@ int corr_candidates_f32(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal
         A.cand_dhi = sink->hi_diag;
         A.defer_args = sink->defer_args;
         A.defer_rsym = sink->defer_rsym;
-        A.cand_tiles = ctx->cand_tiles;
-        A.cand_n_tiles = ctx->cand_n_tiles;
+        A.cand_tiles = sink->tiles;
+        A.cand_n_tiles = sink->n_tiles;
     } else if (!out || !out->d_ptr) {
         return fail(ctx, CS_ERR_INVALID, "candidate mode needs a sink or a map");
     }
@@ -89,49 +159,35 @@ struct CandPlan {
 
 int find_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_kernel* kernel,
                     const cs_normxcorr2_params* p, const cs_foci_params* fp, size_t win_bytes,
-                    size_t (*tail_bytes)(long long), CandPlan* P)
+                    size_t (*tail_bytes)(long long), const int* d_tiles, int n_tiles, CandPlan* P)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc;
-    int rb = 0, re = p->ms;
-    if (p->row_end > p->row_begin) {
-        if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
-        rb = p->row_begin;
-        re = p->row_end;
-    }
+    int rb, re;
+    int rc = row_window_of(ctx, p, &rb, &re);
+    if (rc) return rc;
     // ---- coefficient map in context-owned scratch, with the signal's layout
     const bool f64 = p->compute_dtype == CS_F64;
-    cs_matrix map;
-    map.d_ptr = nullptr;
-    map.dtype = f64 ? CS_F64 : CS_F32;
-    map.layout = signal->layout == CS_LAYOUT_BAND_PADDED ? CS_LAYOUT_BAND : signal->layout;
-    map.row0 = rb;
-    if (signal->layout == CS_LAYOUT_BAND || signal->layout == CS_LAYOUT_BAND_PADDED) {
-        if (fp->hi_diag < fp->lo_diag) return fail(ctx, CS_ERR_INVALID, "empty diagonal range");
-        map.band_lo = fp->lo_diag;
-        map.band_w = fp->hi_diag - fp->lo_diag + 1;
-        map.ld = ((int64_t)map.band_w + 63) / 64 * 64;
-    } else {
-        map.band_lo = map.band_w = 0;
-        map.ld = ((int64_t)p->ns + 15) / 16 * 16;
-    }
+    const bool band_sig = stored_band(signal->layout);
+    if (band_sig && fp->hi_diag < fp->lo_diag) return fail(ctx, CS_ERR_INVALID, "empty diagonal range");
+    cs_matrix map = scan_map(signal->layout, f64 ? CS_F64 : CS_F32, p->ns, fp->lo_diag, fp->hi_diag, rb);
     // 1-D patterns (borders, hairpins: max_dist = 0 in the config, 2 scanned diagonals): a streamed
     // 128-column strip would compute 64 columns for every one it keeps.  Every pixel of the few diagonals
     // is a candidate instead and goes straight to the float64 evaluation (one wave per pixel).
-    const bool narrow = (signal->layout == CS_LAYOUT_BAND || signal->layout == CS_LAYOUT_BAND_PADDED) && map.band_w <= 4;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool narrow = band_sig && map.band_w <= 4;
     auto layout = [&](size_t c_cap) {
-        P->off_cols = al(4 * c_cap);
-        P->off_vals = P->off_cols + al(4 * c_cap);
-        P->off_cnt = P->off_vals + al(8 * c_cap);
-        P->off_win = P->off_cnt + 256;
-        P->off_tail = P->off_win + al(win_bytes);
+        if (c_cap > (size_t)INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%zu)", c_cap);
+        Carve c;
+        c.take(4 * c_cap);                      // rows
+        P->off_cols = c.take(4 * c_cap);
+        P->off_vals = c.take(8 * c_cap);
+        P->off_cnt = c.take(256);
+        P->off_win = c.take(win_bytes);
+        P->off_tail = c.total();
         return ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, P->off_tail + tail_bytes((long long)c_cap));
     };
     P->n_cand = 0;
     if (narrow) {
         const long long n_cand = cs::narrow_band_pixels(rb, re, p->ns, map.band_lo, map.band_w);
-        if (n_cand > INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%lld)", n_cand);
         if (n_cand > 0) {
             rc = layout((size_t)n_cand);
             if (rc) return rc;
@@ -149,36 +205,38 @@ int find_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const c
     // other pixel holds 2.0 and is re-evaluated.  float64 maps hold the coefficient.
     const double margin = std::max(fp->rescore_margin, 1e-4);
     const double thr = f64 ? fp->pearson : fp->pearson - margin;
-    size_t c_cap = std::max<size_t>(1 << 16, (size_t)(re - rb) * (size_t)((signal->layout == CS_LAYOUT_BAND || signal->layout == CS_LAYOUT_BAND_PADDED) ? map.band_w : p->ns) / 256);
+    size_t c_cap = first_cand_room((size_t)(re - rb) * (size_t)(band_sig ? map.band_w : p->ns));
+    // One pass over a list with room for c_cap candidates: the pool laid out, the counter cleared, `launch` enqueued, the count
+    // read back; a list that outgrew its room: once more with room for all.  What `launch` returns ends the passes.
+    auto list_passes = [&](auto&& launch) -> int {
+        while (true) {
+            int rc_ = layout(c_cap);
+            if (rc_) return rc_;
+            char* pool = (char*)ctx->d_pool;
+            long long* d_cnt = (long long*)(pool + P->off_cnt);
+            CS_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, stream));
+            rc_ = launch(pool, d_cnt);
+            if (rc_) return rc_;
+            CS_HIP(ctx, hipMemcpyAsync(ctx->h_counts, d_cnt, 8, hipMemcpyDeviceToHost, stream));
+            CS_HIP(ctx, hipStreamSynchronize(stream));
+            P->n_cand = ctx->h_counts[0];
+            if ((size_t)P->n_cand <= c_cap) return CS_OK;
+            c_cap = (size_t)P->n_cand + (size_t)P->n_cand / 8;
+        }
+    };
     // ---- float32, masked tile kernel: the kernel appends the candidates itself (no map, no compaction pass)
-    bool fused_ok = !f64;
-    while (fused_ok) {
-        if (c_cap > (size_t)INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%zu)", c_cap);
-        rc = layout(c_cap);
-        if (rc) return rc;
-        char* pool = (char*)ctx->d_pool;
-        long long* d_cnt = (long long*)(pool + P->off_cnt);
-        CS_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, stream));
-        CandSink sink{(unsigned long long*)(pool + P->off_vals), (unsigned long long*)d_cnt, (long long)c_cap, 0ull,
-                      fp->lo_diag, fp->hi_diag};
-        rc = corr_candidates_f32(ctx, stream, signal, kernel, p, &map, margin, thr, &sink);
-        if (rc == CS_NEED_MAP) {
-            fused_ok = false;
-            break;
+    if (!f64) {
+        rc = list_passes([&](char* pool, long long* d_cnt) {
+            CandSink sink{(unsigned long long*)(pool + P->off_vals), (unsigned long long*)d_cnt, (long long)c_cap, 0ull,
+                          fp->lo_diag, fp->hi_diag, nullptr, nullptr, d_tiles, n_tiles};
+            return corr_candidates_f32(ctx, stream, signal, kernel, p, &map, margin, thr, &sink);
+        });
+        if (rc == CS_OK && P->n_cand > 0) {
+            char* pool = (char*)ctx->d_pool;
+            rc = cs::launch_decode_keys((const long long*)(pool + P->off_vals), P->n_cand, p->ns, (int*)pool, (int*)(pool + P->off_cols), stream);
+            if (rc) return fail(ctx, CS_ERR_HIP, "key decoding failed: %s", hipGetErrorString((hipError_t)rc));
         }
-        if (rc) return rc;
-        CS_HIP(ctx, hipMemcpyAsync(ctx->h_counts, d_cnt, 8, hipMemcpyDeviceToHost, stream));
-        CS_HIP(ctx, hipStreamSynchronize(stream));
-        P->n_cand = ctx->h_counts[0];
-        if ((size_t)P->n_cand <= c_cap) {
-            if (P->n_cand > 0) {
-                rc = cs::launch_decode_keys((const long long*)(pool + P->off_vals), P->n_cand, p->ns, (int*)pool,
-                                            (int*)(pool + P->off_cols), stream);
-                if (rc) return fail(ctx, CS_ERR_HIP, "key decoding failed: %s", hipGetErrorString((hipError_t)rc));
-            }
-            return CS_OK;
-        }
-        c_cap = (size_t)P->n_cand + (size_t)P->n_cand / 8;      // the list overflowed: once more with room for all
+        if (rc != CS_NEED_MAP) return rc;
     }
     // ---- coefficient map in context scratch, then thresholded compaction
     rc = ensure_scratch(ctx, &ctx->d_map, &ctx->d_map_bytes, map_bytes);
@@ -187,24 +245,11 @@ int find_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const c
     if (f64) rc = cs_normxcorr2(ctx, stream_, signal, kernel, p, &map, nullptr);
     else rc = corr_candidates_f32(ctx, stream, signal, kernel, p, &map, margin, thr, nullptr);
     if (rc) return rc;
-    while (true) {
-        if (c_cap > (size_t)INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%zu)", c_cap);
-        rc = layout(c_cap);
-        if (rc) return rc;
-        char* pool = (char*)ctx->d_pool;
-        long long* d_cnt = (long long*)(pool + P->off_cnt);
-        CS_HIP(ctx, hipMemsetAsync(d_cnt, 0, 16, stream));
-        rc = cs::launch_compact_ge(view_of(&map), f64, re, p->ns, thr, fp->lo_diag, fp->hi_diag, (int*)pool,
-                                   (int*)(pool + P->off_cols), (double*)(pool + P->off_vals), (long long)c_cap, d_cnt,
-                                   ctx->n_cu, stream);
-        if (rc) return fail(ctx, CS_ERR_HIP, "compact launch failed: %s", hipGetErrorString((hipError_t)rc));
-        CS_HIP(ctx, hipMemcpyAsync(ctx->h_counts, d_cnt, 8, hipMemcpyDeviceToHost, stream));
-        CS_HIP(ctx, hipStreamSynchronize(stream));
-        P->n_cand = ctx->h_counts[0];
-        if ((size_t)P->n_cand <= c_cap) break;
-        c_cap = (size_t)P->n_cand + (size_t)P->n_cand / 8;
-    }
-    return CS_OK;
+    return list_passes([&](char* pool, long long* d_cnt) {
+        const int rc_ = cs::launch_compact_ge(view_of(&map), f64, re, p->ns, thr, fp->lo_diag, fp->hi_diag, (int*)pool, (int*)(pool + P->off_cols),
+                                              (double*)(pool + P->off_vals), (long long)c_cap, d_cnt, ctx->n_cu, stream);
+        return rc_ ? fail(ctx, CS_ERR_HIP, "compact launch failed: %s", hipGetErrorString((hipError_t)rc_)) : (int)CS_OK;
+    });
 }
 }  // namespace
 
@@ -224,7 +269,7 @@ int cs_detect_foci(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs
     const int kk = kernel->km * kernel->kn;
     const size_t win_pat = fp->want_windows ? (size_t)std::max<int64_t>(cap, 1) : 0;
     CandPlan P;
-    rc = find_candidates(ctx, stream_, signal, kernel, p, fp, 8 * win_pat * kk, cs::foci_scratch_bytes, &P);
+    rc = find_candidates(ctx, stream_, signal, kernel, p, fp, 8 * win_pat * kk, cs::foci_scratch_bytes, nullptr, 0, &P);
     if (rc) return rc;
     const long long n_cand = P.n_cand;
     if (n_cand == 0) return CS_OK;
@@ -238,18 +283,9 @@ int cs_detect_foci(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs
     cs::FocusRec* d_rec = nullptr;
     // Page-locked output buffers (what cs_host_alloc hands out) are written by the last kernel itself: one
     // stream synchronisation per call instead of a count round trip plus two copies.
-    auto device_view = [&](const void* h) -> void* {
-        if (!h) return nullptr;
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, h) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
-    };
-    cs::FocusRec* rec_direct = cap > 0 ? reinterpret_cast<cs::FocusRec*>(device_view(h_foci)) : nullptr;
-    double* win_direct = (fp->want_windows && h_windows) ? reinterpret_cast<double*>(device_view(h_windows)) : nullptr;
-    const bool direct = rec_direct && (!fp->want_windows || !h_windows || win_direct);
+    cs::FocusRec* rec_direct = nullptr;
+    double* win_direct = nullptr;
+    const bool direct = pinned_views(h_foci, cap, fp->want_windows, h_windows, &rec_direct, &win_direct) && rec_direct;
     if (direct) {
         ctx->h_counts[1] = -1;
         rc = cs::enqueue_foci(A64, (const int*)pool, (const int*)(pool + P.off_cols), n_cand, fp->pearson, fp->min_size,
@@ -329,31 +365,15 @@ int cs_detect_foci_batch_templates(cs_ctx* ctx, void* stream_, int32_t n_blocks,
         }
     const long long n_total = seg[n_virtual];
     if (n_total > INT32_MAX / 2) return fail(ctx, CS_ERR_OVERFLOW, "too many candidate pixels (%lld)", n_total);
-    // results straight into page-locked caller buffers (cs_host_alloc); anything else goes through cs_detect_foci
-    auto device_view = [&](const void* h) -> void* {
-        if (!h) return nullptr;
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, h) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
-    };
-    cs::FocusRec* rec = cap > 0 ? reinterpret_cast<cs::FocusRec*>(device_view(h_foci)) : nullptr;
-    double* win = (foci[0].want_windows && h_windows) ? reinterpret_cast<double*>(device_view(h_windows)) : nullptr;
-    if ((cap > 0 && !rec) || (foci[0].want_windows && h_windows && !win))
-        return fail(ctx, CS_ERR_UNSUPPORTED, "the batch entry writes into page-locked buffers (cs_host_alloc)");
-    // per-block counts through a page-locked array owned by the context
-    const size_t cnt_bytes = 8 * ((size_t)n_virtual + 2);
-    if (cnt_bytes > ctx->h_blk_bytes) {
-        if (ctx->h_blk_counts) CS_HIP(ctx, hipHostFree(ctx->h_blk_counts));
-        ctx->h_blk_counts = nullptr;
-        ctx->h_blk_bytes = 0;
-        CS_HIP(ctx, hipHostMalloc((void**)&ctx->h_blk_counts, 2 * cnt_bytes, hipHostMallocDefault));
-        ctx->h_blk_bytes = 2 * cnt_bytes;
-    }
+    // (anything but page-locked caller buffers goes through cs_detect_foci)
+    cs::FocusRec* rec = nullptr;
+    double* win = nullptr;
+    int rc = batch_views(ctx, h_foci, cap, foci[0].want_windows, h_windows, &rec, &win);
+    if (rc) return rc;
+    rc = ensure_blk_counts(ctx, (size_t)n_virtual);
+    if (rc) return rc;
     ctx->h_blk_counts[0] = -1;
-    int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, cs::narrow_batch_scratch_bytes(n_virtual, n_total));
+    rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, cs::narrow_batch_scratch_bytes(n_virtual, n_total));
     if (rc) return rc;
     rc = cs::enqueue_foci_narrow_batch(tab.data(), seg.data(), lo_w.data(), n_virtual, foci[0].pearson, foci[0].min_size,
                                        diag_code(foci, kernels, params), foci[0].inter, ctx->d_pool, rec, (long long)cap, win,
@@ -432,34 +452,17 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
     if (params[0].compute_dtype != CS_F32) return fail(ctx, CS_ERR_UNSUPPORTED, "the 2-D batch runs the float32 tile kernel");
     if (kernel->km != kernel->kn || kernel->km > 17 || kernel->km < 3 || !(kernel->km & 1))
         return fail(ctx, CS_ERR_UNSUPPORTED, "the masked tile kernel takes odd square templates of 3 .. 17 (caller: block by block)");
-    // results straight into page-locked caller buffers (cs_host_alloc)
-    auto device_view = [&](const void* h) -> void* {
-        if (!h) return nullptr;
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, h) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
-    };
-    cs::FocusRec* rec = cap > 0 ? reinterpret_cast<cs::FocusRec*>(device_view(h_foci)) : nullptr;
-    double* win = (foci[0].want_windows && h_windows) ? reinterpret_cast<double*>(device_view(h_windows)) : nullptr;
-    if ((cap > 0 && !rec) || (foci[0].want_windows && h_windows && !win))
-        return fail(ctx, CS_ERR_UNSUPPORTED, "the batch entry writes into page-locked buffers (cs_host_alloc)");
-    const size_t cnt_bytes = 8 * ((size_t)n_blocks + 2);
-    if (cnt_bytes > ctx->h_blk_bytes) {
-        if (ctx->h_blk_counts) CS_HIP(ctx, hipHostFree(ctx->h_blk_counts));
-        ctx->h_blk_counts = nullptr;
-        ctx->h_blk_bytes = 0;
-        CS_HIP(ctx, hipHostMalloc((void**)&ctx->h_blk_counts, 2 * cnt_bytes, hipHostMallocDefault));
-        ctx->h_blk_bytes = 2 * cnt_bytes;
-    }
+    cs::FocusRec* rec = nullptr;
+    double* win = nullptr;
+    int rc_views = batch_views(ctx, h_foci, cap, foci[0].want_windows, h_windows, &rec, &win);
+    if (!rc_views) rc_views = ensure_blk_counts(ctx, (size_t)n_blocks);
+    if (rc_views) return rc_views;
     laps.lap("checks, pinned views");
     std::vector<cs::CorrArgs<double>> tab;       // the float64 argument blocks of the chain behind the tile kernels
     // ---- candidates of every block into one list
     const double margin = std::max(foci[0].rescore_margin, 1e-4);
     const double thr = foci[0].pearson - margin;
-    size_t c_cap = std::max<size_t>(1 << 16, (size_t)(pixels / 256));
+    size_t c_cap = first_cand_room((size_t)pixels);
     // (tests of the retry and fall-back paths: a first room for the candidates / a bound for the deferred chain's launches that
     // this call's lists outgrow)
     long long seg_min = 2048;
@@ -482,7 +485,6 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
         bool paced;
         ~HintUpdate() { if (on) { c->cand_hint = *n; c->cand_hint_pixels = px; c->cand_hint_blocks = nb; c->cand_hint_paced = paced; } }
     };
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     long long n_total = 0;
     HintUpdate hint_update{ctx, &n_total, (long long)pixels, n_blocks, !prepare_only, same_layout && ctx->cand_hint_paced};
     // SEGMENTED candidate lists: every block appends to a region of its own with a counter of its own (room in proportion to
@@ -511,7 +513,9 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
                 list_cap += (size_t)seg_cap[(size_t)b];
             }
         }
-        const size_t off_cnt = al(8 * list_cap), off_tail = off_cnt + 1024;
+        Carve c;                                        // keys (every block's region) | counters | the chain's scratch
+        c.take(8 * list_cap);
+        const size_t off_cnt = c.take(1024), off_tail = c.total();
         off_tail_now = off_tail;
         segmented = segmented_ok;
         int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, off_tail + cs::keyed_batch_scratch_bytes(n_blocks, (long long)list_cap));
@@ -539,7 +543,7 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
         if (!prepared) CS_HIP(ctx, hipMemsetAsync(d_cnt, 0, kCntBytes, stream));      // (tile kernels go out block by block below)
         int table_rsym = -1;
         if (prepared) {
-            const size_t need = al(cs::mfma_blocks_table_bytes(n_blocks)) + cs::mask_prep_table_bytes(n_blocks);
+            const size_t need = Carve::al(cs::mfma_blocks_table_bytes(n_blocks)) + cs::mask_prep_table_bytes(n_blocks);
             if (need > ctx->tab_bytes) {
                 CS_HIP(ctx, hipDeviceSynchronize());
                 if (ctx->h_tab) CS_HIP(ctx, hipHostFree(ctx->h_tab));
@@ -569,12 +573,12 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
             }
         }
         bool early_tables = false;
+        auto cost = [&](int b) { return (long long)params[b].ms * (foci[b].hi_diag - foci[b].lo_diag + 1); };
         // blocks to lanes: largest first onto the least loaded lane
         std::vector<int> lane_of((size_t)n_blocks, 0);
         if (n_lanes > 1) {
             std::vector<int> order((size_t)n_blocks);
             for (int b = 0; b < n_blocks; ++b) order[b] = b;
-            auto cost = [&](int b) { return (long long)params[b].ms * (foci[b].hi_diag - foci[b].lo_diag + 1); };
             std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost(x) > cost(y); });
             long long load[kBlkLanes] = {};
             for (int b : order) {
@@ -668,9 +672,7 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
         std::vector<int> launch_order((size_t)n_blocks);
         for (int b = 0; b < n_blocks; ++b) launch_order[b] = b;
         if (n_lanes > 1)
-            std::stable_sort(launch_order.begin(), launch_order.end(), [&](int x, int y) {
-                return (long long)params[x].ms * (foci[x].hi_diag - foci[x].lo_diag + 1) > (long long)params[y].ms * (foci[y].hi_diag - foci[y].lo_diag + 1);
-            });
+            std::stable_sort(launch_order.begin(), launch_order.end(), [&](int x, int y) { return cost(x) > cost(y); });
         // one tile launch: the mask tables of all blocks from ONE launch on the side lane (collected in the loop, launched
         // behind it) -- a launch per block takes 30-90 us each beside a genome's staging kernels
         const bool one_prep = table && early_tables;
@@ -714,19 +716,8 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
                 }
             } tab_swap(ctx, prepared ? b : -1);
             const cs_matrix* sig = (signals_f32 && signals_f32[b].d_ptr) ? signals_f32 + b : signals + b;
-            cs_matrix map;                        // geometry of the (virtual) coefficient map: the scanned diagonals
-            map.d_ptr = nullptr;
-            map.dtype = CS_F32;
-            map.layout = is_band(signals[b].layout) ? CS_LAYOUT_BAND : signals[b].layout;
-            map.row0 = 0;
-            if (map.layout == CS_LAYOUT_BAND) {
-                map.band_lo = foci[b].lo_diag;
-                map.band_w = foci[b].hi_diag - foci[b].lo_diag + 1;
-                map.ld = ((int64_t)map.band_w + 63) / 64 * 64;
-            } else {
-                map.band_lo = map.band_w = 0;
-                map.ld = ((int64_t)params[b].ns + 15) / 16 * 16;
-            }
+            // geometry of the (virtual) coefficient map: the scanned diagonals
+            const cs_matrix map = scan_map(signals[b].layout, CS_F32, params[b].ns, foci[b].lo_diag, foci[b].hi_diag, 0);
             CandSink sink{(unsigned long long*)pool, d_cnt, (long long)c_cap, (unsigned long long)b << kKeyShift, foci[b].lo_diag,
                           foci[b].hi_diag};
             if (segmented) {
@@ -754,7 +745,7 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
         if (one_prep) {
             ctx->prep_collect = nullptr;
             if (!reuse) {
-                const size_t tile_tab_bytes = al(cs::mfma_blocks_table_bytes(n_blocks));
+                const size_t tile_tab_bytes = Carve::al(cs::mfma_blocks_table_bytes(n_blocks));
                 int rcp = 0;
                 if (prep_carries) {
                     // the lane the tile launch waits for: ONE upload (tile table + mask-table arguments, neighbours in h_tab / d_tab)
@@ -932,150 +923,136 @@ int cs_detect_foci_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs
     return CS_OK;
 }
 
-int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_kernel* kernel,
-                  const cs_normxcorr2_params* p, const cs_foci_params* fp, int32_t* h_rows, int32_t* h_cols,
-                  double* h_vals, int64_t cap, int64_t* n_out)
+namespace {
+// What cs_candidates fills: room for `cap` candidates, *n of them found.
+struct CandOut {
+    int32_t *rows, *cols;
+    double* vals;
+    int64_t cap, *n;
+};
+
+// The host keep-and-order step of a short candidate list with float64 scores: threshold, row-major order, copy-out.
+static int keep_on_host(cs_ctx* ctx, double pearson, const int32_t* rows, const int32_t* cols, const double* vals, size_t m, const CandOut& out)
 {
-    CS_ENTER(ctx);
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_foci_args(ctx, signal, kernel, p, fp);
-    if (rc) return rc;
-    if (!n_out || cap < 0 || (cap > 0 && (!h_rows || !h_cols || !h_vals))) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
-    *n_out = 0;
-    // ---- One synchronisation for the usual case (a 2-D pattern in float32 arithmetic on a kernel with a candidate sink, a few hundred
-    // candidates): tile kernel -> the first n_first keys decoded and re-scored in float64, bounded by the DEVICE's count, written with the count
-    // into a mapped host block -> threshold and order on the host.  The general flow below reads the count first (to size
-    // what follows), sorts and compacts on the device and synchronises three times: 0.14 ms that a rank's share of a row-split block
-    // waited for behind a 0.23 ms tile kernel (profiles/r06_c4p_split_shares.txt).  A list longer than the key list's capacity, or a
-    // kernel without a sink, takes the general flow.
-    const bool band_sig = signal->layout == CS_LAYOUT_BAND || signal->layout == CS_LAYOUT_BAND_PADDED;
-    if (p->compute_dtype == CS_F32 && !(band_sig && fp->hi_diag - fp->lo_diag + 1 <= 4) && fp->hi_diag >= fp->lo_diag &&
-        !std::getenv("CHROMOSIGHT_HIP_NO_SMALL_KEEP")) {
-        constexpr long long kHeads = 32768;                      // room of the host block and of the heads' device arrays
-        // how many keys the ONE launch covers: the previous call's count on this context and a quarter (a whole 200 000-bin block
-        // has ~ 15 000 candidates before the float64 scores thin them out; its second call needs no second round), at least 8192
-        const long long n_first = std::min<long long>(kHeads, std::max<long long>(8192, ctx->cand_prev + ctx->cand_prev / 4 + 64));
-        int rb = 0, re = p->ms;
-        if (p->row_end > p->row_begin) {
-            if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
-            rb = p->row_begin;
-            re = p->row_end;
-        }
-        cs_matrix map;                                          // the output geometry of the sink (no storage)
-        map.d_ptr = nullptr;
-        map.dtype = CS_F32;
-        map.layout = band_sig ? CS_LAYOUT_BAND : signal->layout;
-        map.row0 = rb;
-        map.band_lo = band_sig ? fp->lo_diag : 0;
-        map.band_w = band_sig ? fp->hi_diag - fp->lo_diag + 1 : 0;
-        map.ld = band_sig ? ((int64_t)map.band_w + 63) / 64 * 64 : ((int64_t)p->ns + 15) / 16 * 16;
-        const bool plain_layout = band_sig || signal->layout == CS_LAYOUT_DENSE;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t c_cap = std::max<size_t>(1 << 16, (size_t)(re - rb) * (size_t)(band_sig ? map.band_w : p->ns) / 256);
-        // device scratch: keys[c_cap] | count | (heads: in the host block) | a second round's rows, cols, vals
-        // ('count' = the copy of the device's counter that travels with the heads; the counters themselves: ctx->d_cand_cnt)
-        const size_t off_cnt = al(8 * c_cap), off_rows = off_cnt + 256, off_cols = off_rows + al(4 * kHeads), off_vals = off_cols + al(4 * kHeads);
-        const size_t rest = c_cap;                             // (a second round holds at most c_cap - 8192)
-        const size_t off_rows2 = off_vals + al(8 * kHeads), off_cols2 = off_rows2 + al(4 * rest), off_vals2 = off_cols2 + al(4 * rest);
-        const size_t h_bytes = 256 + 4 * kHeads + 4 * kHeads + 8 * kHeads;
-        rc = plain_layout ? ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, off_vals2 + al(8 * rest)) : CS_ERR_UNSUPPORTED;
-        if (rc == CS_OK && !ctx->h_small) {
-            if (hipHostMalloc(&ctx->h_small, h_bytes, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->h_small = nullptr;
-                rc = CS_ERR_HIP;
-            }
-        }
-        if (rc == CS_OK && !ctx->d_cand_cnt) {
-            if (hipMalloc((void**)&ctx->d_cand_cnt, 512) != hipSuccess) {
-                (void)hipGetLastError();
-                ctx->d_cand_cnt = nullptr;
-                rc = CS_ERR_HIP;
-            }
-            ctx->cand_cnt_clean = false;
-        }
-        if (rc == CS_OK) {
-            char* pool = (char*)ctx->d_pool;
-            unsigned long long* d_keys = (unsigned long long*)pool;
-            if (!ctx->cand_cnt_clean) CS_HIP(ctx, hipMemsetAsync(ctx->d_cand_cnt, 0, 512, stream));
-            ctx->cand_cnt_clean = false;                        // (until this call's kernels are known to have run)
-            long long* d_cnt = ctx->d_cand_cnt + 32 * ctx->cand_cnt_phase;
-            long long* d_cnt_next = ctx->d_cand_cnt + 32 * (ctx->cand_cnt_phase ^ 1);
-            const double margin = std::max(fp->rescore_margin, 1e-4);
-            CandSink sink{d_keys, (unsigned long long*)d_cnt, (long long)c_cap, 0ull, fp->lo_diag, fp->hi_diag};
-            rc = corr_candidates_f32(ctx, stream, signal, kernel, p, &map, margin, fp->pearson - margin, &sink);
-            if (rc == CS_OK) {
-                int* h_rows_small = (int*)((char*)ctx->h_small + 256);
-                int* h_cols_small = (int*)((char*)ctx->h_small + 256 + (off_cols - off_rows));
-                double* h_vals_small = (double*)((char*)ctx->h_small + 256 + (off_vals - off_rows));
-                cs::CorrArgs<double> A64;
-                rc = build_args<double>(ctx, stream, signal, kernel, p, &A64);
-                if (rc) return rc;
-                // keys -> pixels and float64 scores of the first min(n_first, count) of them; the count lands next to them and the
-                // other counter is cleared for the next call
-                // -- written by the kernel straight into the page-locked host block (h_small is mapped and coherent: a few hundred
-                // 4- and 8-byte stores over the link instead of a 9 us wait for the copy engine and an 8 us copy)
-                rc = cs::launch_rescore_f64_keys(A64, (const long long*)d_keys, p->ns, n_first, h_rows_small, h_cols_small, h_vals_small, d_cnt,
-                                                 (long long*)ctx->h_small, d_cnt_next, stream);
-                if (rc) return fail(ctx, CS_ERR_HIP, "candidate kernels failed: %s", hipGetErrorString((hipError_t)rc));
-                char* h = (char*)ctx->h_small;
-                CS_HIP(ctx, hipStreamSynchronize(stream));
-                ctx->cand_cnt_phase ^= 1;
-                ctx->cand_cnt_clean = true;
-                const long long n_cand = *reinterpret_cast<const long long*>(h);
-                ctx->cand_prev = n_cand;
-                if (n_cand <= (long long)c_cap) {
-                    const int32_t* rows = reinterpret_cast<const int32_t*>(h + 256);
-                    const int32_t* cols = reinterpret_cast<const int32_t*>(h + 256 + (off_cols - off_rows));
-                    const double* vals = reinterpret_cast<const double*>(h + 256 + (off_vals - off_rows));
-                    // a list longer than the heads (a whole 200 000-bin block: ~ 15 000 candidates before the float64 scores thin them
-                    // out): the rest is decoded and re-scored from the SAME key list -- the tile kernel does not run again -- and
-                    // arrives with a second synchronisation
-                    std::vector<int32_t> rows2, cols2;
-                    std::vector<double> vals2;
-                    const long long m2 = std::max(0ll, n_cand - n_first);
-                    if (m2 > 0) {
-                        int* d_r2 = (int*)(pool + off_rows2);
-                        int* d_c2 = (int*)(pool + off_cols2);
-                        double* d_v2 = (double*)(pool + off_vals2);
-                        rc = cs::launch_decode_keys((const long long*)d_keys + n_first, m2, p->ns, d_r2, d_c2, stream);
-                        if (rc) return fail(ctx, CS_ERR_HIP, "key decoding failed: %s", hipGetErrorString((hipError_t)rc));
-                        rc = cs::launch_rescore_f64(A64, d_r2, d_c2, m2, d_v2, nullptr, stream);
-                        if (rc) return fail(ctx, CS_ERR_HIP, "candidate kernels failed: %s", hipGetErrorString((hipError_t)rc));
-                        rows2.resize((size_t)m2);
-                        cols2.resize((size_t)m2);
-                        vals2.resize((size_t)m2);
-                        CS_HIP(ctx, hipMemcpyAsync(rows2.data(), d_r2, 4 * (size_t)m2, hipMemcpyDeviceToHost, stream));
-                        CS_HIP(ctx, hipMemcpyAsync(cols2.data(), d_c2, 4 * (size_t)m2, hipMemcpyDeviceToHost, stream));
-                        CS_HIP(ctx, hipMemcpyAsync(vals2.data(), d_v2, 8 * (size_t)m2, hipMemcpyDeviceToHost, stream));
-                        CS_HIP(ctx, hipStreamSynchronize(stream));
-                    }
-                    auto row_of = [&](uint32_t t) { return t < (uint32_t)n_first ? rows[t] : rows2[t - (uint32_t)n_first]; };
-                    auto col_of = [&](uint32_t t) { return t < (uint32_t)n_first ? cols[t] : cols2[t - (uint32_t)n_first]; };
-                    auto val_of = [&](uint32_t t) { return t < (uint32_t)n_first ? vals[t] : vals2[t - (uint32_t)n_first]; };
-                    std::vector<uint32_t> keep;
-                    keep.reserve((size_t)n_cand);
-                    for (long long t = 0; t < n_cand; ++t)
-                        if (val_of((uint32_t)t) >= fp->pearson && val_of((uint32_t)t) != 0.0) keep.push_back((uint32_t)t);      // (flag_keep_kernel's rule)
-                    std::sort(keep.begin(), keep.end(),
-                              [&](uint32_t a, uint32_t b) { return row_of(a) != row_of(b) ? row_of(a) < row_of(b) : col_of(a) < col_of(b); });
-                    *n_out = (int64_t)keep.size();
-                    if ((int64_t)keep.size() > cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld candidates, room for %lld", (long long)keep.size(), (long long)cap);
-                    for (size_t t = 0; t < keep.size(); ++t) {
-                        h_rows[t] = row_of(keep[t]);
-                        h_cols[t] = col_of(keep[t]);
-                        h_vals[t] = val_of(keep[t]);
-                    }
-                    return CS_OK;
-                }
-                // (more candidates than the key list holds: the general flow, which sizes its list by the count)
-            } else if (rc != CS_NEED_MAP) {
-                return rc;
-            }
-        }
+    std::vector<uint32_t> keep;
+    keep.reserve(m);
+    for (size_t t = 0; t < m; ++t)
+        if (vals[t] >= pearson && vals[t] != 0.0) keep.push_back((uint32_t)t);          // (flag_keep_kernel's rule)
+    std::sort(keep.begin(), keep.end(), [&](uint32_t a, uint32_t b) { return rows[a] != rows[b] ? rows[a] < rows[b] : cols[a] < cols[b]; });
+    *out.n = (int64_t)keep.size();
+    if ((int64_t)keep.size() > out.cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld candidates, room for %lld", (long long)keep.size(), (long long)out.cap);
+    for (size_t t = 0; t < keep.size(); ++t) {
+        out.rows[t] = rows[keep[t]];
+        out.cols[t] = cols[keep[t]];
+        out.vals[t] = vals[keep[t]];
     }
+    return CS_OK;
+}
+
+// ---- One synchronisation for the usual case (a 2-D pattern in float32 arithmetic on a kernel with a candidate sink, a few hundred
+// candidates): tile kernel -> the first n_first keys decoded and re-scored in float64, bounded by the DEVICE's count, written with the count
+// into a mapped host block -> threshold and order on the host.  The general flow reads the count first (to size
+// what follows), sorts and compacts on the device and synchronises three times: 0.14 ms that a rank's share of a row-split block
+// waited for behind a 0.23 ms tile kernel (profiles/r06_c4p_split_shares.txt).  A list longer than the key list's capacity, or a
+// kernel without a sink, takes the general flow: kGeneralFlow instead of CS_OK.
+constexpr int kGeneralFlow = CS_NEED_MAP + 1;
+static int candidates_one_sync(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const cs_kernel* kernel, const cs_normxcorr2_params* p,
+                        const cs_foci_params* fp, const int* d_tiles, int n_tiles, const CandOut& out)
+{
+    // how many keys the ONE launch covers: the previous call's count on this context and a quarter (a whole 200 000-bin block
+    // has ~ 15 000 candidates before the float64 scores thin them out; its second call needs no second round), at least 8192
+    const long long n_first = std::min<long long>(kHeads, std::max<long long>(8192, ctx->cand_prev + ctx->cand_prev / 4 + 64));
+    int rb, re;
+    int rc = row_window_of(ctx, p, &rb, &re);
+    if (rc) return rc;
+    const bool band_sig = stored_band(signal->layout);
+    const cs_matrix map = scan_map(signal->layout, CS_F32, p->ns, fp->lo_diag, fp->hi_diag, rb);      // the output geometry of the sink
+    const bool plain_layout = band_sig || signal->layout == CS_LAYOUT_DENSE;
+    const size_t c_cap = first_cand_room((size_t)(re - rb) * (size_t)(band_sig ? map.band_w : p->ns));
+    // device scratch: keys[c_cap] | count | (heads: in the host block) | a second round's rows, cols, vals
+    // ('count' = the copy of the device's counter that travels with the heads; the counters themselves: ctx->d_cand_cnt)
+    const size_t rest = c_cap;                             // (a second round holds at most c_cap - 8192)
+    Carve c;
+    c.take(8 * c_cap);
+    c.take(256);
+    const size_t off_rows = c.take(4 * kHeads), off_cols = c.take(4 * kHeads), off_vals = c.take(8 * kHeads);
+    const size_t off_rows2 = c.take(4 * rest), off_cols2 = c.take(4 * rest), off_vals2 = c.take(8 * rest);
+    const size_t h_bytes = 256 + 4 * kHeads + 4 * kHeads + 8 * kHeads;
+    rc = plain_layout ? ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, c.total()) : CS_ERR_UNSUPPORTED;
+    if (rc == CS_OK && !ctx->h_small && hipHostMalloc(&ctx->h_small, h_bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->h_small = nullptr;
+        rc = CS_ERR_HIP;
+    }
+    if (rc == CS_OK && !ctx->d_cand_cnt) {
+        if (hipMalloc((void**)&ctx->d_cand_cnt, 512) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->d_cand_cnt = nullptr;
+            rc = CS_ERR_HIP;
+        }
+        ctx->cand_cnt_clean = false;
+    }
+    if (rc != CS_OK) return kGeneralFlow;
+    char* pool = (char*)ctx->d_pool;
+    unsigned long long* d_keys = (unsigned long long*)pool;
+    if (!ctx->cand_cnt_clean) CS_HIP(ctx, hipMemsetAsync(ctx->d_cand_cnt, 0, 512, stream));
+    ctx->cand_cnt_clean = false;                        // (until this call's kernels are known to have run)
+    long long* d_cnt = ctx->d_cand_cnt + 32 * ctx->cand_cnt_phase;
+    long long* d_cnt_next = ctx->d_cand_cnt + 32 * (ctx->cand_cnt_phase ^ 1);
+    const double margin = std::max(fp->rescore_margin, 1e-4);
+    CandSink sink{d_keys, (unsigned long long*)d_cnt, (long long)c_cap, 0ull, fp->lo_diag, fp->hi_diag, nullptr, nullptr, d_tiles, n_tiles};
+    rc = corr_candidates_f32(ctx, stream, signal, kernel, p, &map, margin, fp->pearson - margin, &sink);
+    if (rc) return rc == CS_NEED_MAP ? kGeneralFlow : rc;
+    char* h = (char*)ctx->h_small;
+    int32_t* rows = (int32_t*)(h + 256);
+    int32_t* cols = (int32_t*)(h + 256 + (off_cols - off_rows));
+    double* vals = (double*)(h + 256 + (off_vals - off_rows));
+    cs::CorrArgs<double> A64;
+    rc = build_args<double>(ctx, stream, signal, kernel, p, &A64);
+    if (rc) return rc;
+    // keys -> pixels and float64 scores of the first min(n_first, count) of them; the count lands next to them and the
+    // other counter is cleared for the next call
+    // -- written by the kernel straight into the page-locked host block (h_small is mapped and coherent: a few hundred
+    // 4- and 8-byte stores over the link instead of a 9 us wait for the copy engine and an 8 us copy)
+    rc = cs::launch_rescore_f64_keys(A64, (const long long*)d_keys, p->ns, n_first, rows, cols, vals, d_cnt,
+                                     (long long*)ctx->h_small, d_cnt_next, stream);
+    if (rc) return fail(ctx, CS_ERR_HIP, "candidate kernels failed: %s", hipGetErrorString((hipError_t)rc));
+    CS_HIP(ctx, hipStreamSynchronize(stream));
+    ctx->cand_cnt_phase ^= 1;
+    ctx->cand_cnt_clean = true;
+    const long long n_cand = *reinterpret_cast<const long long*>(h);
+    ctx->cand_prev = n_cand;
+    if (n_cand > (long long)c_cap) return kGeneralFlow;         // (more candidates than the key list holds: the general flow, which sizes its list by the count)
+    // a list longer than the heads (a whole 200 000-bin block: ~ 15 000 candidates before the float64 scores thin them
+    // out): the rest is decoded and re-scored from the SAME key list -- the tile kernel does not run again -- and
+    // arrives with a second synchronisation, behind a copy of the heads
+    std::vector<int32_t> rows2, cols2;
+    std::vector<double> vals2;
+    const long long m2 = std::max(0ll, n_cand - n_first);
+    if (m2 > 0) {
+        int *d_r2 = (int*)(pool + off_rows2), *d_c2 = (int*)(pool + off_cols2);
+        double* d_v2 = (double*)(pool + off_vals2);
+        rc = cs::launch_decode_keys((const long long*)d_keys + n_first, m2, p->ns, d_r2, d_c2, stream);
+        if (rc) return fail(ctx, CS_ERR_HIP, "key decoding failed: %s", hipGetErrorString((hipError_t)rc));
+        rc = cs::launch_rescore_f64(A64, d_r2, d_c2, m2, d_v2, nullptr, stream);
+        if (rc) return fail(ctx, CS_ERR_HIP, "candidate kernels failed: %s", hipGetErrorString((hipError_t)rc));
+        rows2.assign(rows, rows + n_first), cols2.assign(cols, cols + n_first), vals2.assign(vals, vals + n_first);
+        rows2.resize((size_t)n_cand), cols2.resize((size_t)n_cand), vals2.resize((size_t)n_cand);
+        CS_HIP(ctx, hipMemcpyAsync(rows2.data() + n_first, d_r2, 4 * (size_t)m2, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipMemcpyAsync(cols2.data() + n_first, d_c2, 4 * (size_t)m2, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipMemcpyAsync(vals2.data() + n_first, d_v2, 8 * (size_t)m2, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipStreamSynchronize(stream));
+        rows = rows2.data(), cols = cols2.data(), vals = vals2.data();
+    }
+    return keep_on_host(ctx, fp->pearson, rows, cols, vals, (size_t)n_cand, out);
+}
+
+// The general flow: the count is read first and sizes what follows (find_candidates).
+static int candidates_general(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const cs_kernel* kernel, const cs_normxcorr2_params* p,
+                       const cs_foci_params* fp, const int* d_tiles, int n_tiles, bool small_keep, const CandOut& out)
+{
     CandPlan P;
-    rc = find_candidates(ctx, stream_, signal, kernel, p, fp, 0, cs::keep_scratch_bytes, &P);
+    int rc = find_candidates(ctx, stream, signal, kernel, p, fp, 0, cs::keep_scratch_bytes, d_tiles, n_tiles, &P);
     if (rc) return rc;
     if (P.n_cand == 0) return CS_OK;
     cs::CorrArgs<double> A64;
@@ -1083,7 +1060,7 @@ int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
     if (rc) return rc;
     char* pool = (char*)ctx->d_pool;
     constexpr long long kSmallList = 16384;
-    if (P.n_cand <= kSmallList && !std::getenv("CHROMOSIGHT_HIP_NO_SMALL_KEEP")) {
+    if (P.n_cand <= kSmallList && small_keep) {
         // A short candidate list (a 2-D pattern: 1e-5 of the scanned pixels) is re-scored as it came -- unsorted -- downloaded with ONE
         // synchronisation and thresholded and ordered on the host: the device form below costs a dozen launches (keys, a three-pass
         // sort, decode, flags, scan, scatter, decode), a count read-back and a second synchronisation, which is what a rank's share of a
@@ -1098,20 +1075,9 @@ int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
         CS_HIP(ctx, hipMemcpyAsync(cols.data(), pool + P.off_cols, 4 * m, hipMemcpyDeviceToHost, stream));
         CS_HIP(ctx, hipMemcpyAsync(vals.data(), d_vals, 8 * m, hipMemcpyDeviceToHost, stream));
         CS_HIP(ctx, hipStreamSynchronize(stream));
-        std::vector<uint32_t> keep;
-        keep.reserve(m);
-        for (size_t t = 0; t < m; ++t)
-            if (vals[t] >= fp->pearson && vals[t] != 0.0) keep.push_back((uint32_t)t);          // (flag_keep_kernel's rule)
-        std::sort(keep.begin(), keep.end(), [&](uint32_t a, uint32_t b) { return rows[a] != rows[b] ? rows[a] < rows[b] : cols[a] < cols[b]; });
-        *n_out = (int64_t)keep.size();
-        if ((int64_t)keep.size() > cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld candidates, room for %lld", (long long)keep.size(), (long long)cap);
-        for (size_t t = 0; t < keep.size(); ++t) {
-            h_rows[t] = rows[keep[t]];
-            h_cols[t] = cols[keep[t]];
-            h_vals[t] = vals[keep[t]];
-        }
-        return CS_OK;
+        return keep_on_host(ctx, fp->pearson, rows.data(), cols.data(), vals.data(), m, out);
     }
+    // ... a long one: kept, ordered and compacted on the device
     int *d_rows = nullptr, *d_cols = nullptr, *d_n = nullptr;
     double* d_vals = nullptr;
     rc = cs::enqueue_keep(A64, (const int*)pool, (const int*)(pool + P.off_cols), P.n_cand, fp->pearson, pool + P.off_tail,
@@ -1121,15 +1087,41 @@ int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_
     CS_HIP(ctx, hipMemcpyAsync(h_n, d_n, 4, hipMemcpyDeviceToHost, stream));
     CS_HIP(ctx, hipStreamSynchronize(stream));
     const long long n = *h_n;
-    *n_out = n;
-    if (n > cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld candidates, room for %lld", n, (long long)cap);
+    *out.n = n;
+    if (n > out.cap) return fail(ctx, CS_ERR_OVERFLOW, "%lld candidates, room for %lld", n, (long long)out.cap);
     if (n > 0) {
-        CS_HIP(ctx, hipMemcpyAsync(h_rows, d_rows, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-        CS_HIP(ctx, hipMemcpyAsync(h_cols, d_cols, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
-        CS_HIP(ctx, hipMemcpyAsync(h_vals, d_vals, 8 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipMemcpyAsync(out.rows, d_rows, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipMemcpyAsync(out.cols, d_cols, 4 * (size_t)n, hipMemcpyDeviceToHost, stream));
+        CS_HIP(ctx, hipMemcpyAsync(out.vals, d_vals, 8 * (size_t)n, hipMemcpyDeviceToHost, stream));
         CS_HIP(ctx, hipStreamSynchronize(stream));
     }
     return CS_OK;
+}
+
+// cs_candidates and cs_candidates_tiles behind their checks (d_tiles: the device tile list of the latter, or null).
+static int candidates(cs_ctx* ctx, hipStream_t stream, const cs_matrix* signal, const cs_kernel* kernel, const cs_normxcorr2_params* p,
+               const cs_foci_params* fp, const int* d_tiles, int n_tiles, const CandOut& out)
+{
+    const bool small_keep = !std::getenv("CHROMOSIGHT_HIP_NO_SMALL_KEEP");          // (per call: tests flip it in-process)
+    const bool narrow = stored_band(signal->layout) && fp->hi_diag - fp->lo_diag + 1 <= 4;
+    if (small_keep && p->compute_dtype == CS_F32 && !narrow && fp->hi_diag >= fp->lo_diag) {
+        int rc = candidates_one_sync(ctx, stream, signal, kernel, p, fp, d_tiles, n_tiles, out);
+        if (rc != kGeneralFlow) return rc;
+    }
+    return candidates_general(ctx, stream, signal, kernel, p, fp, d_tiles, n_tiles, small_keep, out);
+}
+}  // namespace
+
+int cs_candidates(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_kernel* kernel,
+                  const cs_normxcorr2_params* p, const cs_foci_params* fp, int32_t* h_rows, int32_t* h_cols,
+                  double* h_vals, int64_t cap, int64_t* n_out)
+{
+    CS_ENTER(ctx);
+    int rc = check_foci_args(ctx, signal, kernel, p, fp);
+    if (rc) return rc;
+    if (!n_out || cap < 0 || (cap > 0 && (!h_rows || !h_cols || !h_vals))) return fail(ctx, CS_ERR_INVALID, "bad output buffers");
+    *n_out = 0;
+    return candidates(ctx, (hipStream_t)stream_, signal, kernel, p, fp, nullptr, 0, CandOut{h_rows, h_cols, h_vals, cap, n_out});
 }
 
 int cs_candidates_tiles(cs_ctx* ctx, void* stream_, const cs_matrix* signal, const cs_kernel* kernel,
@@ -1142,12 +1134,9 @@ int cs_candidates_tiles(cs_ctx* ctx, void* stream_, const cs_matrix* signal, con
     if (n_tiles < 0 || (n_tiles > 0 && !d_tiles)) return fail(ctx, CS_ERR_INVALID, "bad tile list");
     if (signal->layout != CS_LAYOUT_DENSE) return fail(ctx, CS_ERR_UNSUPPORTED, "a tile list needs a dense signal (the 64 x 64 grid of a dense map)");
     *n_out = 0;
-    int rb = 0, re = p->ms;
-    if (p->row_end > p->row_begin) {
-        if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
-        rb = p->row_begin;
-        re = p->row_end;
-    }
+    int rb, re;
+    int rc = row_window_of(ctx, p, &rb, &re);
+    if (rc) return rc;
     const long long tiles_x = ((long long)p->ns + 63) / 64, tiles_y = ((long long)(re - rb) + 63) / 64;
     if (n_tiles == 0) return CS_OK;                 // no tile a stored pixel reaches: no candidate
     // the list on the host: checked (the list instance of the tile kernel indexes its grid with it) and, for the kernels that
@@ -1162,11 +1151,9 @@ int cs_candidates_tiles(cs_ctx* ctx, void* stream_, const cs_matrix* signal, con
             return fail(ctx, CS_ERR_INVALID, "tile %d of the list (%d) outside the %lld x %lld grid", t, tiles[(size_t)t], tiles_y, tiles_x);
         listed[(size_t)tiles[(size_t)t]] = 1;
     }
-    ctx->cand_tiles = d_tiles;
-    ctx->cand_n_tiles = n_tiles;
-    int rc = cs_candidates(ctx, stream_, signal, kernel, p, fp, h_rows, h_cols, h_vals, cap, n_out);
-    ctx->cand_tiles = nullptr;
-    ctx->cand_n_tiles = 0;
+    rc = check_foci_args(ctx, signal, kernel, p, fp);
+    if (rc) return rc;
+    rc = candidates(ctx, stream, signal, kernel, p, fp, d_tiles, n_tiles, CandOut{h_rows, h_cols, h_vals, cap, n_out});
     if (rc) return rc;
     int64_t k = 0;
     for (int64_t t = 0; t < *n_out; ++t) {
@@ -1216,10 +1203,10 @@ int cs_label_foci_route(cs_ctx* ctx, void* stream_, int32_t ms, int32_t ns, cons
     if (route != 0)                 // (the one-workgroup forms threshold their list and drop exact zeros: not the list given)
         for (int64_t t = 0; t < n; ++t)
             if (h_vals[t] == 0.0) return fail(ctx, CS_ERR_INVALID, "candidate %lld has the value 0", (long long)t);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t un = (size_t)n;
-    const size_t off_cols = al(4 * un), off_vals = off_cols + al(4 * un), off_cnt = off_vals + al(8 * un),
-                 off_tail = off_cnt + 256;
+    Carve c;                                        // rows | cols | vals | counter | the labelling's scratch
+    c.take(4 * un);
+    const size_t off_cols = c.take(4 * un), off_vals = c.take(8 * un), off_cnt = c.take(256), off_tail = c.total();
     int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, off_tail + cs::label_scratch_bytes(n));
     if (rc) return rc;
     char* pool = (char*)ctx->d_pool;
@@ -1256,12 +1243,12 @@ int cs_quantify_pixels(cs_ctx* ctx, void* stream_, const cs_matrix* signal, cons
     if (n < 0 || (n > 0 && (!h_rows || !h_cols || !h_out))) return fail(ctx, CS_ERR_INVALID, "bad pixel list");
     if (n == 0) return CS_OK;
     const int kk = kernel->km * kernel->kn;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t un = (size_t)n;
-    const size_t off_cols = al(4 * un), off_score = off_cols + al(4 * un), off_nobs = off_score + al(8 * un),
-                 off_rec = off_nobs + al(8 * un), off_win = off_rec + al(sizeof(cs::FocusRec) * un),
-                 total = off_win + (fp->want_windows ? al(8 * un * kk) : 0);
-    rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, total);
+    Carve c;                                        // rows | cols | scores | present pixels | records | windows
+    c.take(4 * un);
+    const size_t off_cols = c.take(4 * un), off_score = c.take(8 * un), off_nobs = c.take(8 * un),
+                 off_rec = c.take(sizeof(cs::FocusRec) * un), off_win = c.take(fp->want_windows ? 8 * un * kk : 0);
+    rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, c.total());
     if (rc) return rc;
     char* pool = (char*)ctx->d_pool;
     CS_HIP(ctx, hipMemcpyAsync(pool, h_rows, 4 * un, hipMemcpyHostToDevice, stream));
@@ -1279,6 +1266,55 @@ int cs_quantify_pixels(cs_ctx* ctx, void* stream_, const cs_matrix* signal, cons
     return CS_OK;
 }
 
+namespace {
+// What cs_quantify_blocks and cs_pileup_blocks share: n positions, t = pixel (h_rows[t], h_cols[t]) of sub-matrix h_blk[t].
+// The blocks are checked (float64 arithmetic, or the entry's `f64_only`) and the positions; with n > 0 the pool is laid out as
+// blk | rows | cols | inter | tab | the entry's own pieces (own_bytes, at `own`), the blocks' argument and inter tables
+// are built and the five are uploaded.  The tables are pageable: they live here until the entry has synchronised.
+struct PositionList {
+    const int *d_blk, *d_rows, *d_cols, *d_inter;
+    const cs::CorrArgs<double>* d_tab;
+    char* own;
+    std::vector<cs::CorrArgs<double>> tab;
+    std::vector<int> inter;
+};
+
+static int stage_positions(cs_ctx* ctx, hipStream_t stream, int32_t n_blocks, const cs_matrix* signals, const cs_kernel* kernel,
+                    const cs_normxcorr2_params* params, const cs_foci_params* foci, const int32_t* h_blk, const int32_t* h_rows,
+                    const int32_t* h_cols, int64_t n, const char* f64_only, size_t own_bytes, PositionList* L)
+{
+    for (int b = 0; b < n_blocks; ++b) {
+        int rc = check_foci_args(ctx, signals + b, kernel, params + b, foci + b);
+        if (rc) return rc;
+        if (params[b].compute_dtype != CS_F64) return fail(ctx, CS_ERR_UNSUPPORTED, "%s", f64_only);
+    }
+    for (int64_t t = 0; t < n; ++t)
+        if (h_blk[t] < 0 || h_blk[t] >= n_blocks) return fail(ctx, CS_ERR_INVALID, "pixel %lld names sub-matrix %d of %d", (long long)t, h_blk[t], n_blocks);
+    if (n == 0) return CS_OK;
+    const size_t un = (size_t)n, nb = (size_t)n_blocks;
+    Carve c;
+    const size_t off_blk = c.take(4 * un), off_rows = c.take(4 * un), off_cols = c.take(4 * un), off_inter = c.take(4 * nb),
+                 off_tab = c.take(sizeof(cs::CorrArgs<double>) * nb);
+    int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, c.total() + own_bytes);
+    if (rc) return rc;
+    char* pool = (char*)ctx->d_pool;
+    *L = PositionList{(int*)(pool + off_blk), (int*)(pool + off_rows), (int*)(pool + off_cols), (int*)(pool + off_inter),
+                      (cs::CorrArgs<double>*)(pool + off_tab), pool + c.total(), std::vector<cs::CorrArgs<double>>(nb),
+                      std::vector<int>(nb)};
+    for (int b = 0; b < n_blocks; ++b) {
+        rc = build_args<double>(ctx, stream, signals + b, kernel, params + b, &L->tab[(size_t)b]);
+        if (rc) return rc;
+        L->inter[(size_t)b] = foci[b].inter;
+    }
+    CS_HIP(ctx, hipMemcpyAsync((void*)L->d_blk, h_blk, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync((void*)L->d_rows, h_rows, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync((void*)L->d_cols, h_cols, 4 * un, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync((void*)L->d_inter, L->inter.data(), 4 * nb, hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync((void*)L->d_tab, L->tab.data(), sizeof(cs::CorrArgs<double>) * nb, hipMemcpyHostToDevice, stream));
+    return CS_OK;
+}
+}  // namespace
+
 // quantify mode over the sub-matrices of a genome in ONE launch chain (one call per template instead of one per
 // sub-matrix and template: cli/chromosight.py:229-260 scores one sub-matrix per task)
 int cs_quantify_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs_matrix* signals, const cs_kernel* kernel,
@@ -1289,43 +1325,20 @@ int cs_quantify_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs_ma
     hipStream_t stream = (hipStream_t)stream_;
     if (n_blocks <= 0 || !signals || !kernel || !params || !foci) return fail(ctx, CS_ERR_INVALID, "bad batch arguments");
     if (n < 0 || (n > 0 && (!h_blk || !h_rows || !h_cols || !h_out))) return fail(ctx, CS_ERR_INVALID, "bad pixel list");
-    for (int b = 0; b < n_blocks; ++b) {
-        int rc = check_foci_args(ctx, signals + b, kernel, params + b, foci + b);
-        if (rc) return rc;
-        if (params[b].compute_dtype != CS_F64) return fail(ctx, CS_ERR_UNSUPPORTED, "quantify scores in float64");
-    }
-    for (int64_t t = 0; t < n; ++t)
-        if (h_blk[t] < 0 || h_blk[t] >= n_blocks) return fail(ctx, CS_ERR_INVALID, "pixel %lld names sub-matrix %d of %d", (long long)t, h_blk[t], n_blocks);
-    if (n == 0) return CS_OK;
     const bool want_windows = foci[0].want_windows && h_windows;
-    const int kk = kernel->km * kernel->kn;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t un = (size_t)n, nb = (size_t)n_blocks;
-    const size_t off_rows = al(4 * un), off_cols = off_rows + al(4 * un), off_inter = off_cols + al(4 * un),
-                 off_tab = off_inter + al(4 * nb), off_score = off_tab + al(sizeof(cs::CorrArgs<double>) * nb),
-                 off_nobs = off_score + al(8 * un), off_rec = off_nobs + al(8 * un), off_win = off_rec + al(sizeof(cs::FocusRec) * un),
-                 total = off_win + (want_windows ? al(8 * un * kk) : 0);
-    int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, total);
-    if (rc) return rc;
-    char* pool = (char*)ctx->d_pool;
-    std::vector<cs::CorrArgs<double>> tab(nb);
-    std::vector<int> inter(nb);
-    for (int b = 0; b < n_blocks; ++b) {
-        rc = build_args<double>(ctx, stream, signals + b, kernel, params + b, &tab[(size_t)b]);
-        if (rc) return rc;
-        inter[(size_t)b] = foci[b].inter;
-    }
-    CS_HIP(ctx, hipMemcpyAsync(pool, h_blk, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_rows, h_rows, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_cols, h_cols, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_inter, inter.data(), 4 * nb, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_tab, tab.data(), sizeof(cs::CorrArgs<double>) * nb, hipMemcpyHostToDevice, stream));
-    double* d_win = want_windows ? (double*)(pool + off_win) : nullptr;
-    rc = cs::enqueue_quantify_batch((const cs::CorrArgs<double>*)(pool + off_tab), (const int*)(pool + off_inter), (const int*)pool,
-                                    (const int*)(pool + off_rows), (const int*)(pool + off_cols), n, (double*)(pool + off_score),
-                                    (double*)(pool + off_nobs), (cs::FocusRec*)(pool + off_rec), d_win, stream);
+    const size_t un = (size_t)n, kk = (size_t)kernel->km * kernel->kn;
+    Carve own;                                      // behind the positions: scores | present pixels | records | windows
+    const size_t off_score = own.take(8 * un), off_nobs = own.take(8 * un), off_rec = own.take(sizeof(cs::FocusRec) * un),
+                 off_win = own.take(want_windows ? 8 * un * kk : 0);
+    PositionList L;
+    int rc = stage_positions(ctx, stream, n_blocks, signals, kernel, params, foci, h_blk, h_rows, h_cols, n, "quantify scores in float64",
+                             own.total(), &L);
+    if (rc || n == 0) return rc;
+    double* d_win = want_windows ? (double*)(L.own + off_win) : nullptr;
+    rc = cs::enqueue_quantify_batch(L.d_tab, L.d_inter, L.d_blk, L.d_rows, L.d_cols, n, (double*)(L.own + off_score),
+                                    (double*)(L.own + off_nobs), (cs::FocusRec*)(L.own + off_rec), d_win, stream);
     if (rc) return fail(ctx, CS_ERR_HIP, "quantify kernels failed: %s", hipGetErrorString((hipError_t)rc));
-    CS_HIP(ctx, hipMemcpyAsync(h_out, pool + off_rec, sizeof(cs_focus) * un, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipMemcpyAsync(h_out, L.own + off_rec, sizeof(cs_focus) * un, hipMemcpyDeviceToHost, stream));
     if (d_win) CS_HIP(ctx, hipMemcpyAsync(h_windows, d_win, 8 * un * kk, hipMemcpyDeviceToHost, stream));
     CS_HIP(ctx, hipStreamSynchronize(stream));       // (the pageable tables above were consumed)
     return CS_OK;
@@ -1345,46 +1358,23 @@ int cs_pileup_blocks(cs_ctx* ctx, void* stream_, int32_t n_blocks, const cs_matr
     if (n_blocks <= 0 || !signals || !kernel || !params || !foci || !h_sum || !h_cnt) return fail(ctx, CS_ERR_INVALID, "bad batch arguments");
     if (n < 0 || (n > 0 && (!h_blk || !h_rows || !h_cols))) return fail(ctx, CS_ERR_INVALID, "bad pixel list");
     if (n > INT32_MAX) return fail(ctx, CS_ERR_OVERFLOW, "too many pixels (%lld)", (long long)n);
-    for (int b = 0; b < n_blocks; ++b) {
-        int rc = check_foci_args(ctx, signals + b, kernel, params + b, foci + b);
-        if (rc) return rc;
-        if (params[b].compute_dtype != CS_F64) return fail(ctx, CS_ERR_UNSUPPORTED, "windows are read in float64");
-    }
-    for (int64_t t = 0; t < n; ++t)
-        if (h_blk[t] < 0 || h_blk[t] >= n_blocks) return fail(ctx, CS_ERR_INVALID, "pixel %lld names sub-matrix %d of %d", (long long)t, h_blk[t], n_blocks);
     const int kk = kernel->km * kernel->kn;
-    const size_t ukk = (size_t)kk;
+    const size_t ukk = (size_t)kk, nc = (size_t)cs::pileup_chunks(n);
+    Carve own;                                      // behind the positions: the chunks' partial sums and counts | sums | counts
+    const size_t off_psum = own.take(8 * nc * ukk), off_pcnt = own.take(8 * nc * ukk), off_sum = own.take(8 * ukk), off_cnt = own.take(8 * ukk);
+    PositionList L;
+    int rc = stage_positions(ctx, stream, n_blocks, signals, kernel, params, foci, h_blk, h_rows, h_cols, n, "windows are read in float64",
+                             own.total(), &L);
+    if (rc) return rc;
     if (n == 0) {
         for (size_t e = 0; e < ukk; ++e) h_sum[e] = 0.0, h_cnt[e] = 0;
         return CS_OK;
     }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t un = (size_t)n, nb = (size_t)n_blocks, nc = (size_t)cs::pileup_chunks(n);
-    const size_t off_rows = al(4 * un), off_cols = off_rows + al(4 * un), off_inter = off_cols + al(4 * un),
-                 off_tab = off_inter + al(4 * nb), off_psum = off_tab + al(sizeof(cs::CorrArgs<double>) * nb),
-                 off_pcnt = off_psum + al(8 * nc * ukk), off_sum = off_pcnt + al(8 * nc * ukk), off_cnt = off_sum + al(8 * ukk),
-                 total = off_cnt + al(8 * ukk);
-    int rc = ensure_scratch(ctx, &ctx->d_pool, &ctx->d_pool_bytes, total);
-    if (rc) return rc;
-    char* pool = (char*)ctx->d_pool;
-    std::vector<cs::CorrArgs<double>> tab(nb);
-    std::vector<int> inter(nb);
-    for (int b = 0; b < n_blocks; ++b) {
-        rc = build_args<double>(ctx, stream, signals + b, kernel, params + b, &tab[(size_t)b]);
-        if (rc) return rc;
-        inter[(size_t)b] = foci[b].inter;
-    }
-    CS_HIP(ctx, hipMemcpyAsync(pool, h_blk, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_rows, h_rows, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_cols, h_cols, 4 * un, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_inter, inter.data(), 4 * nb, hipMemcpyHostToDevice, stream));
-    CS_HIP(ctx, hipMemcpyAsync(pool + off_tab, tab.data(), sizeof(cs::CorrArgs<double>) * nb, hipMemcpyHostToDevice, stream));
-    rc = cs::enqueue_pileup_batch((const cs::CorrArgs<double>*)(pool + off_tab), (const int*)(pool + off_inter), (const int*)pool,
-                                  (const int*)(pool + off_rows), (const int*)(pool + off_cols), n, kk, (double*)(pool + off_psum),
-                                  (long long*)(pool + off_pcnt), (double*)(pool + off_sum), (long long*)(pool + off_cnt), stream);
+    rc = cs::enqueue_pileup_batch(L.d_tab, L.d_inter, L.d_blk, L.d_rows, L.d_cols, n, kk, (double*)(L.own + off_psum),
+                                  (long long*)(L.own + off_pcnt), (double*)(L.own + off_sum), (long long*)(L.own + off_cnt), stream);
     if (rc) return fail(ctx, CS_ERR_HIP, "pileup kernels failed: %s", hipGetErrorString((hipError_t)rc));
-    CS_HIP(ctx, hipMemcpyAsync(h_sum, pool + off_sum, 8 * ukk, hipMemcpyDeviceToHost, stream));
-    CS_HIP(ctx, hipMemcpyAsync(h_cnt, pool + off_cnt, 8 * ukk, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipMemcpyAsync(h_sum, L.own + off_sum, 8 * ukk, hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipMemcpyAsync(h_cnt, L.own + off_cnt, 8 * ukk, hipMemcpyDeviceToHost, stream));
     CS_HIP(ctx, hipStreamSynchronize(stream));       // (the pageable tables above were consumed)
     return CS_OK;
 }

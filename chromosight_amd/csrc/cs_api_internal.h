@@ -106,8 +106,6 @@ struct cs_ctx {
     int cand_cnt_phase = 0;               // re-scoring kernel of one call clears the counter of the next (no memset in the chain);
     bool cand_cnt_clean = false;          // false until a call has gone through: both are cleared before use
     long long cand_prev = 0;              // candidates of the previous cs_candidates call on this context (sizes the next call's one launch)
-    const int* cand_tiles = nullptr;      // cs_candidates_tiles: the device tile list the candidate sink's tile kernel walks (CorrArgs::cand_tiles)
-    int cand_n_tiles = 0;
     long long* h_cand_counts = nullptr;   // pinned, 256 entries (cs_detect_foci_blocks, segmented lists): [b] the blocks' own candidate counts, [60] their
                                           // clamped total, [61] status flags; [64 + b] / [128 + b]: the regions' starts / rooms the device reads
     void* d_counts_peak = nullptr;   // cs_normxcorr2_host: largest |pixel| of the map (float bits), and its pinned copy
@@ -322,6 +320,17 @@ struct AllowCounts {
         if (c) c->allow_counts = was;
     }
 };
+
+// the output rows [*rb, *re) of a call: its row window, or the whole matrix
+static inline int row_window_of(cs_ctx* ctx, const cs_normxcorr2_params* p, int* rb, int* re)
+{
+    *rb = 0, *re = p->ms;
+    if (p->row_end > p->row_begin) {
+        if (p->row_begin < 0 || p->row_end > p->ms) return fail(ctx, CS_ERR_INVALID, "row window outside the matrix");
+        *rb = p->row_begin, *re = p->row_end;
+    }
+    return CS_OK;
+}
 
 // grow-only device scratch of a context
 int ensure_scratch(cs_ctx* ctx, void** buf, size_t* have, size_t need);

@@ -123,30 +123,12 @@ def run_rescore(dev, sig, shape, kspec, rows, cols, *, full, sym_upper, max_dist
     n = rows.size
     if n == 0:
         return np.zeros(0), np.zeros(0)
-    params = CsNormxcorr2Params(
-        int(shape[0]), int(shape[1]), int(bool(full)), int(bool(sym_upper)),
-        -1 if max_dist is None else int(max_dist), int(mask_mode),
-        miss_row.ptr if miss_row is not None else None,
-        miss_col.ptr if miss_col is not None else None,
-        mask.ptr if mask is not None else None,
-        min_present((kspec.km, kspec.kn), missing_tol), CS_F64, XCORR_THRESHOLD, DENOM_EPS,
-    )
+    params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, mask, missing_tol, CS_F64)
     d_rows, d_cols = dev.to_device(rows), dev.to_device(cols)
     d_r, d_n = dev.empty(n, np.float64), dev.empty(n, np.float64)
     dev._check(dev.lib.cs_rescore_f64(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params),
                                       d_rows.ptr, d_cols.ptr, n, d_r.ptr, d_n.ptr))
     return d_r.download(stream), d_n.download(stream)
-
-
-# Detect mode on float32 maps (csrc/cs_device.h cand_screen_*): a pixel is re-evaluated in float64 on the device when its
-# float32 coefficient is within RESCORE_MARGIN of the threshold, OR when its window is too ill-conditioned for the float32
-# error to stay below a quarter of that margin (variance of the window relative to its mean square, or of the template over
-# the present pixels, below 8 n 2^-24 / margin = 2.8e-3 for a 17 x 17 template), OR when one of its sums sits next to one of
-# the reference's zeroing thresholds; the exact values are then thresholded.  The candidate set is a superset of the pixels
-# whose exact coefficient passes whatever the data look like (tests/test_gpu_margin.py).
-RESCORE_MARGIN = 0.05
-
-
 
 
 def map_pitch(width, itemsize=4, quantum=16):
@@ -169,6 +151,15 @@ def to_device_map(dev, array, stream=None):
     padded = np.zeros((array.shape[0], ld), dtype=array.dtype)
     padded[:, :array.shape[1]] = array
     return dev.to_device(padded, stream=stream), ld
+
+
+# Detect mode on float32 maps (csrc/cs_device.h cand_screen_*): a pixel is re-evaluated in float64 on the device when its
+# float32 coefficient is within RESCORE_MARGIN of the threshold, OR when its window is too ill-conditioned for the float32
+# error to stay below a quarter of that margin (variance of the window relative to its mean square, or of the template over
+# the present pixels, below 8 n 2^-24 / margin = 2.8e-3 for a 17 x 17 template), OR when one of its sums sits next to one of
+# the reference's zeroing thresholds; the exact values are then thresholded.  The candidate set is a superset of the pixels
+# whose exact coefficient passes whatever the data look like (tests/test_gpu_margin.py).
+RESCORE_MARGIN = 0.05
 # below this threshold most pixels of a float32 map would be candidates: such maps are computed in float64
 LOW_PEARSON_F64 = 0.1
 
@@ -205,6 +196,31 @@ def _host_buffers(dev, cap, kk, want_windows):
     return rec, win
 
 
+def _copy_out(rec, win, k, kspec, want_windows):
+    """Copies of the first k records of the pinned buffers and of their windows (None without windows)."""
+    windows = win.reshape(-1)[:k * kspec.km * kspec.kn].reshape(k, kspec.km, kspec.kn).copy() if want_windows else None
+    return rec[:k].copy(), windows
+
+
+def _call_with_room(cap, count, call):
+    """The entries that fill caller buffers: call(cap) -> (rc, room, result) runs one with buffers for at least `cap` results
+    (`room`: what they really hold).  CS_ERR_OVERFLOW (-4) with count() > room -- more results than room --: once more, with a
+    quarter more than count().  Returns (rc, result) of the last call; rc is the caller's to check."""
+    while True:
+        rc, room, result = call(cap)
+        if rc != -4 or count() <= room:
+            return rc, result
+        cap = int(count()) + int(count()) // 4
+
+
+def _into_pinned(dev, kspec, want_windows, entry):
+    """A call of _call_with_room on the device's pinned buffers: entry(records, room, windows or None) -> rc; result (rec, win)."""
+    def call(cap):
+        rec, win = _host_buffers(dev, cap, kspec.km * kspec.kn, want_windows)
+        return entry(rec.ctypes.data, rec.shape[0], win.ctypes.data if want_windows else None), rec.shape[0], (rec, win)
+    return call
+
+
 @_one_call_per_context
 def run_detect_foci(dev, sig, shape, kspec, *, pearson, lo_diag, hi_diag, inter, diag_only, full, sym_upper, max_dist,
                     mask_mode=MASK_NONE, miss_row=None, miss_col=None, missing_tol=0.75, precision=None,
@@ -217,24 +233,12 @@ def run_detect_foci(dev, sig, shape, kspec, *, pearson, lo_diag, hi_diag, inter,
                           compute_code(precision))
     fp = CsFociParams(float(pearson), rescore_margin(pearson), int(min_size), int(bool(diag_only)), int(lo_diag), int(hi_diag),
                       int(bool(inter)), int(bool(want_windows)))
-    kk = kspec.km * kspec.kn
-    cap = 4096
-    while True:
-        rec, win = _host_buffers(dev, cap, kk, want_windows)
-        cap = rec.shape[0]
-        n = C.c_int64(0)
-        rc = dev.lib.cs_detect_foci(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp),
-                                    rec.ctypes.data, cap, C.byref(n), win.ctypes.data if want_windows else None)
-        if rc == -4 and n.value > cap:          # CS_ERR_OVERFLOW: more foci than records
-            cap = int(n.value) + int(n.value) // 4
-            continue
-        dev._check(rc)
-        break
-    k = int(n.value)
-    windows = None
-    if want_windows:
-        windows = win.reshape(-1)[:k * kk].reshape(k, kspec.km, kspec.kn).copy()
-    return rec[:k].copy(), windows
+    n = C.c_int64(0)
+    rc, (rec, win) = _call_with_room(4096, lambda: n.value, _into_pinned(dev, kspec, want_windows, lambda rec, cap, win: (
+        dev.lib.cs_detect_foci(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp), rec, cap,
+                               C.byref(n), win))))
+    dev._check(rc)
+    return _copy_out(rec, win, int(n.value), kspec, want_windows)
 
 
 def _block_arrays(dev, sigs, sigs32, shapes, kspec, max_dists, miss_rows, miss_cols, missing_tol, code, sym_upper):
@@ -309,33 +313,25 @@ def run_detect_foci_batch(dev, sigs, shapes, kspec, *, pearson, hi_diags, inter,
                                              flat=True)
             dev._check(rc2)
             cnt = np.frombuffer(counts, dtype=np.int64).copy()
-            total = int(cnt.sum())
-            windows = win.reshape(-1)[:total * kk].reshape(total, kspec.km, kspec.kn).copy() if want_windows else None
-            return rec[:total].copy(), windows, cnt
+            return _copy_out(rec, win, int(cnt.sum()), kspec, want_windows) + (cnt,)
 
         return finish
-    while True:
-        rec, win = _host_buffers(dev, cap, kk, want_windows)
-        cap = rec.shape[0]
-        if kspecs is not None:
-            rc = dev.lib.cs_detect_foci_batch_templates(dev.ctx, stream, n_blocks, sig_arr, n_templates, k_arr, par_arr, fp_arr,
-                                                        rec.ctypes.data, cap, counts, win.ctypes.data if want_windows else None)
-        else:
-            rc = dev.lib.cs_detect_foci_batch(dev.ctx, stream, n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr,
-                                              rec.ctypes.data, cap, counts, win.ctypes.data if want_windows else None)
-        if rc == -3:
-            return None
-        if rc == -4 and sum(counts) > cap:
-            cap = int(sum(counts)) + int(sum(counts)) // 4
-            continue
-        dev._check(rc)
-        break
+    if kspecs is not None:
+        def entry(rec, cap, win):
+            return dev.lib.cs_detect_foci_batch_templates(dev.ctx, stream, n_blocks, sig_arr, n_templates, k_arr, par_arr, fp_arr,
+                                                          rec, cap, counts, win)
+    else:
+        def entry(rec, cap, win):
+            return dev.lib.cs_detect_foci_batch(dev.ctx, stream, n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr, rec,
+                                                cap, counts, win)
+    rc, (rec, win) = _call_with_room(cap, lambda: sum(counts), _into_pinned(dev, kspec, want_windows, entry))
+    if rc == -3:
+        return None
+    dev._check(rc)
     cnt = np.frombuffer(counts, dtype=np.int64).copy()
-    total = int(cnt.sum())
     if flat:
         # all records (and windows) in block order + the per-block counts: the caller post-processes them in one go
-        windows = win.reshape(-1)[:total * kk].reshape(total, kspec.km, kspec.kn).copy() if want_windows else None
-        return rec[:total].copy(), windows, cnt
+        return _copy_out(rec, win, int(cnt.sum()), kspec, want_windows) + (cnt,)
     out, o = [], 0
     flat_w = win.reshape(-1) if want_windows else None
     for b in range(n_blocks):
@@ -362,24 +358,36 @@ def run_detect_foci_blocks(dev, sigs, sigs32, shapes, kspec, *, pearson, lo_diag
         CsFociParams(float(pearson), rescore_margin(pearson), int(min_size), int(bool(diag_only)), int(lo_diags[b]), int(hi_diags[b]),
                      int(bool(inter)), int(bool(want_windows)), int(bool(exclusive)), 0) for b in range(n_blocks)])
     counts = (C.c_int64 * n_blocks)()
-    kk = kspec.km * kspec.kn
-    cap = 4096
-    while True:
-        rec, win = _host_buffers(dev, cap, kk, want_windows)
-        cap = rec.shape[0]
-        rc = dev.lib.cs_detect_foci_blocks(dev.ctx, stream, n_blocks, sig_arr, s32_arr, C.byref(kspec.struct), par_arr, fp_arr,
-                                           rec.ctypes.data, cap, counts, win.ctypes.data if want_windows else None)
-        if rc == -3:
-            return None
-        if rc == -4 and sum(counts) > cap:
-            cap = int(sum(counts)) + int(sum(counts)) // 4
-            continue
-        dev._check(rc)
-        break
+    rc, (rec, win) = _call_with_room(4096, lambda: sum(counts), _into_pinned(dev, kspec, want_windows, lambda rec, cap, win: (
+        dev.lib.cs_detect_foci_blocks(dev.ctx, stream, n_blocks, sig_arr, s32_arr, C.byref(kspec.struct), par_arr, fp_arr, rec, cap,
+                                      counts, win))))
+    if rc == -3:
+        return None
+    dev._check(rc)
     cnt = np.frombuffer(counts, dtype=np.int64).copy()
-    total = int(cnt.sum())
-    windows = win.reshape(-1)[:total * kk].reshape(total, kspec.km, kspec.kn).copy() if want_windows else None
-    return rec[:total].copy(), windows, cnt
+    return _copy_out(rec, win, int(cnt.sum()), kspec, want_windows) + (cnt,)
+
+
+def _candidates(dev, sig, shape, kspec, row_window, tiles, n_tiles, pearson, lo_diag, hi_diag, inter, full, sym_upper, max_dist,
+                mask_mode, miss_row, miss_col, missing_tol, precision, stream):
+    """run_candidates (tiles is None: cs_candidates) and run_candidates_tiles (cs_candidates_tiles)."""
+    if float(pearson) <= LOW_PEARSON_F64:
+        precision = "f64"
+    params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, None, missing_tol,
+                          compute_code(precision), row_window)
+    fp = CsFociParams(float(pearson), rescore_margin(pearson), 1, 0, int(lo_diag), int(hi_diag), int(bool(inter)), 0)
+    head = (dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp))
+    n = C.c_int64(0)
+
+    def call(cap):
+        out = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.float64)
+        room = tuple(a.ctypes.data for a in out) + (cap, C.byref(n))
+        if tiles is None:
+            return dev.lib.cs_candidates(*head, *room), cap, out
+        return dev.lib.cs_candidates_tiles(*head, tiles.ptr if n_tiles else None, int(n_tiles), *room), cap, out
+    rc, out = _call_with_room(1 << 14, lambda: n.value, call)
+    dev._check(rc)
+    return tuple(a[:int(n.value)] for a in out)
 
 
 @_one_call_per_context
@@ -389,25 +397,8 @@ def run_candidates(dev, sig, shape, kspec, row_window, *, pearson, lo_diag, hi_d
     """First half of detect mode on a row window of a sub-matrix (cs_candidates): coordinates and
     float64 coefficients of the pixels of rows row_window[0] <= i < row_window[1] that pass the
     threshold, row-major.  `sig` holds those rows and the template's halo (CsMatrix.row0)."""
-    if float(pearson) <= LOW_PEARSON_F64:
-        precision = "f64"
-    params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, None, missing_tol,
-                          compute_code(precision), row_window)
-    fp = CsFociParams(float(pearson), rescore_margin(pearson), 1, 0, int(lo_diag), int(hi_diag), int(bool(inter)), 0)
-    cap = 1 << 14
-    while True:
-        rows, cols = np.empty(cap, np.int32), np.empty(cap, np.int32)
-        vals = np.empty(cap, np.float64)
-        n = C.c_int64(0)
-        rc = dev.lib.cs_candidates(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp),
-                                   rows.ctypes.data, cols.ctypes.data, vals.ctypes.data, cap, C.byref(n))
-        if rc == -4 and n.value > cap:
-            cap = int(n.value) + int(n.value) // 4
-            continue
-        dev._check(rc)
-        break
-    k = int(n.value)
-    return rows[:k], cols[:k], vals[:k]
+    return _candidates(dev, sig, shape, kspec, row_window, None, 0, pearson, lo_diag, hi_diag, inter, full, sym_upper, max_dist,
+                       mask_mode, miss_row, miss_col, missing_tol, precision, stream)
 
 
 @_one_call_per_context
@@ -431,26 +422,8 @@ def run_candidates_tiles(dev, sig, shape, kspec, row_window, tiles, n_tiles, *, 
                          **_unused):
     """run_candidates on the tiles of a device list only (cs_candidates_tiles; `tiles`: anything with .ptr, n_tiles int32 tile
     indices of the dense grid of row_window -- what run_tile_occupancy returns)."""
-    if float(pearson) <= LOW_PEARSON_F64:
-        precision = "f64"
-    params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, None, missing_tol,
-                          compute_code(precision), row_window)
-    fp = CsFociParams(float(pearson), rescore_margin(pearson), 1, 0, int(lo_diag), int(hi_diag), int(bool(inter)), 0)
-    cap = 1 << 14
-    while True:
-        rows, cols = np.empty(cap, np.int32), np.empty(cap, np.int32)
-        vals = np.empty(cap, np.float64)
-        n = C.c_int64(0)
-        rc = dev.lib.cs_candidates_tiles(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params), C.byref(fp),
-                                         tiles.ptr if n_tiles else None, int(n_tiles), rows.ctypes.data, cols.ctypes.data,
-                                         vals.ctypes.data, cap, C.byref(n))
-        if rc == -4 and n.value > cap:
-            cap = int(n.value) + int(n.value) // 4
-            continue
-        dev._check(rc)
-        break
-    k = int(n.value)
-    return rows[:k], cols[:k], vals[:k]
+    return _candidates(dev, sig, shape, kspec, row_window, tiles, n_tiles, pearson, lo_diag, hi_diag, inter, full, sym_upper,
+                       max_dist, mask_mode, miss_row, miss_col, missing_tol, precision, stream)
 
 
 @_one_call_per_context
@@ -483,13 +456,23 @@ def run_quantify_pixels(dev, sig, shape, kspec, rows, cols, *, inter, full, sym_
     k = rows.size
     params = _corr_params(shape, kspec, full, sym_upper, max_dist, mask_mode, miss_row, miss_col, None, missing_tol, CS_F64)
     fp = CsFociParams(0.0, 0.0, 1, 0, 0, 0, int(bool(inter)), int(bool(want_windows)))
-    kk = kspec.km * kspec.kn
-    rec, win = _host_buffers(dev, max(k, 1), kk, want_windows)
+    rec, win = _host_buffers(dev, max(k, 1), kspec.km * kspec.kn, want_windows)
     dev._check(dev.lib.cs_quantify_pixels(dev.ctx, stream, C.byref(sig), C.byref(kspec.struct), C.byref(params),
                                           C.byref(fp), rows.ctypes.data, cols.ctypes.data, k, rec.ctypes.data,
                                           win.ctypes.data if want_windows else None))
-    windows = win.reshape(-1)[:k * kk].reshape(k, kspec.km, kspec.kn).copy() if want_windows else None
-    return rec[:k].copy(), windows
+    return _copy_out(rec, win, k, kspec, want_windows)
+
+
+def _position_blocks(blocks, kspec, missing_tol, want_windows):
+    """What the position-list entries (cs_quantify_blocks, cs_pileup_blocks) take of the staged blocks: n_blocks, their
+    cs_matrix array, the template, their cs_normxcorr2_params and cs_foci_params arrays."""
+    n_blocks = len(blocks)
+    sig_arr = (_lib.CsMatrix * n_blocks)(*[b.sig for b in blocks])
+    par_arr = (CsNormxcorr2Params * n_blocks)(*[
+        _corr_params(b.shape, kspec, True, not b.inter, b.max_dist, MASK_BINS, b.miss_row, b.miss_col, None, missing_tol, CS_F64)
+        for b in blocks])
+    fp_arr = (CsFociParams * n_blocks)(*[CsFociParams(0.0, 0.0, 1, 0, 0, 0, int(bool(b.inter)), int(bool(want_windows))) for b in blocks])
+    return n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr
 
 
 @_one_call_per_context
@@ -497,22 +480,13 @@ def run_quantify_blocks(dev, blocks, kspec, blk, rows, cols, *, missing_tol=0.75
     """quantify mode over MANY staged sub-matrices with one native call (cs_quantify_blocks): position t is pixel
     (rows[t], cols[t]) of blocks[blk[t]] (pipeline.StagedBlock: intra blocks banded or dense, inter blocks dense -- `inter`
     and `max_dist` per block).  One record (and window) per position, in input order."""
-    blk = np.ascontiguousarray(blk, dtype=np.int32)
-    rows = np.ascontiguousarray(rows, dtype=np.int32)
-    cols = np.ascontiguousarray(cols, dtype=np.int32)
-    k, n_blocks = rows.size, len(blocks)
-    sig_arr = (_lib.CsMatrix * n_blocks)(*[b.sig for b in blocks])
-    par_arr = (CsNormxcorr2Params * n_blocks)(*[
-        _corr_params(b.shape, kspec, True, not b.inter, b.max_dist, MASK_BINS, b.miss_row, b.miss_col, None, missing_tol, CS_F64)
-        for b in blocks])
-    fp_arr = (CsFociParams * n_blocks)(*[CsFociParams(0.0, 0.0, 1, 0, 0, 0, int(bool(b.inter)), int(bool(want_windows))) for b in blocks])
-    kk = kspec.km * kspec.kn
-    rec, win = _host_buffers(dev, max(k, 1), kk, want_windows)
-    dev._check(dev.lib.cs_quantify_blocks(dev.ctx, stream, n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr, blk.ctypes.data,
+    blk, rows, cols = (np.ascontiguousarray(a, dtype=np.int32) for a in (blk, rows, cols))
+    k = rows.size
+    rec, win = _host_buffers(dev, max(k, 1), kspec.km * kspec.kn, want_windows)
+    dev._check(dev.lib.cs_quantify_blocks(dev.ctx, stream, *_position_blocks(blocks, kspec, missing_tol, want_windows), blk.ctypes.data,
                                           rows.ctypes.data, cols.ctypes.data, k, rec.ctypes.data,
                                           win.ctypes.data if want_windows else None))
-    windows = win.reshape(-1)[:k * kk].reshape(k, kspec.km, kspec.kn).copy() if want_windows else None
-    return rec[:k].copy(), windows
+    return _copy_out(rec, win, k, kspec, want_windows)
 
 
 @_one_call_per_context
@@ -521,22 +495,14 @@ def run_pileup_blocks(dev, blocks, kshape, blk, rows, cols, stream=None):
     is pixel (rows[t], cols[t]) of blocks[blk[t]], as in run_quantify_blocks; kshape = (km, kn).  Returns (sum (km, kn) float64,
     cnt (km, kn) int64): per window pixel the sum of its non-NaN values over the positions and their number, summed in the fixed
     order of include/chromosight_hip.h (bitwise reproducible)."""
-    blk = np.ascontiguousarray(blk, dtype=np.int32)
-    rows = np.ascontiguousarray(rows, dtype=np.int32)
-    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    blk, rows, cols = (np.ascontiguousarray(a, dtype=np.int32) for a in (blk, rows, cols))
     km, kn = int(kshape[0]), int(kshape[1])
     # (the windows depend on the template's shape alone: any template of that shape names them)
     kspec = KernelSpec(np.arange(km * kn, dtype=np.float64).reshape(km, kn))
-    k, n_blocks = rows.size, len(blocks)
-    sig_arr = (_lib.CsMatrix * n_blocks)(*[b.sig for b in blocks])
-    par_arr = (CsNormxcorr2Params * n_blocks)(*[
-        _corr_params(b.shape, kspec, True, not b.inter, b.max_dist, MASK_BINS, b.miss_row, b.miss_col, None, 0.75, CS_F64)
-        for b in blocks])
-    fp_arr = (CsFociParams * n_blocks)(*[CsFociParams(0.0, 0.0, 1, 0, 0, 0, int(bool(b.inter)), 0) for b in blocks])
     total = np.empty((km, kn), dtype=np.float64)
     count = np.empty((km, kn), dtype=np.int64)
-    dev._check(dev.lib.cs_pileup_blocks(dev.ctx, stream, n_blocks, sig_arr, C.byref(kspec.struct), par_arr, fp_arr, blk.ctypes.data,
-                                        rows.ctypes.data, cols.ctypes.data, k, total.ctypes.data, count.ctypes.data))
+    dev._check(dev.lib.cs_pileup_blocks(dev.ctx, stream, *_position_blocks(blocks, kspec, 0.75, False), blk.ctypes.data,
+                                        rows.ctypes.data, cols.ctypes.data, rows.size, total.ctypes.data, count.ctypes.data))
     return total, count
 
 

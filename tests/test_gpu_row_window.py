@@ -217,6 +217,114 @@ def test_valid_mode_row_windows(precision):
 
 
 # ------------------------------------------------------------------------------------------------
+# the flows of cs_candidates on the masked tile kernel (17 x 17)
+# ------------------------------------------------------------------------------------------------
+def _noise_band(n, md, seed):
+    """A banded float32 map of n bins: gamma noise, five planted blobs, ~ 3 % missing bins (zeroed rows and columns)."""
+    rng = np.random.default_rng(seed)
+    bw = md + 17 + 1
+    ld = (bw + 4 + 63) // 64 * 64
+    band = np.zeros((n, ld), dtype=np.float32)
+    d = np.arange(bw)
+    band[:, :bw] = np.minimum(rng.gamma(20, 0.05, size=(n, bw)), 10.0)
+    ii, jj = np.indices((17, 17))
+    blob = 1.0 + 2.5 * np.exp(-((ii - 8) ** 2 + (jj - 8) ** 2) / 20.0)
+    for i0, d0 in [(n // 9, 100), (n // 3, 30), (n // 2, 140), (2 * n // 3, 60), (n - 80, 20)]:
+        rr, cc = i0 - 8 + ii, d0 + jj - ii                  # (row, diagonal) of the blob's pixels
+        ok = (cc >= 0) & (cc < bw)
+        band[rr[ok], cc[ok]] *= blob[ok].astype(np.float32)
+    miss = (rng.random(n) < 0.03).astype(np.uint8)
+    band[miss.astype(bool)] = 0
+    for i in range(n):
+        cols = i + d
+        band[i, :bw][(cols >= n) | miss[np.minimum(cols, n - 1)].astype(bool)] = 0
+    return band, bw, ld, miss
+
+
+def _same(a, b):
+    return all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b)) and np.array_equal(a[2].view(np.int64), b[2].view(np.int64))
+
+
+def test_candidate_flows_on_the_masked_tile_kernel(monkeypatch):
+    """cs_candidates / cs_candidates_tiles under the 17 x 17 loops template on the masked matrix-core tile kernel (kernel 5; the
+    flow test of tests/test_gpu_wide.py runs the 21 x 21 two-pass kernel): the one-synchronisation flow, its second round and
+    the general flow with the device keep (CHROMOSIGHT_HIP_NO_SMALL_KEEP=1) return the same rows, columns and float64 values bit
+    for bit, on a whole banded map with missing bins and on an interior row window off the 64-row grid; a tile list given to one
+    call does not linger on the context.
+    The long list: the float64 oracle (oracle/c_oracle.py normxcorr2_band) counts 8041 pixels >= 0.115 and 10956 >= 0.105 on
+    the 1500-bin map below (4086 on 600 bins: too few above LOW_PEARSON_F64; 9357 in the row window), and 22804 >= 0.105 - margin:
+    inside the first room of 1 << 16 keys."""
+    dev = get_device()
+    kspec = engine.KernelSpec(np.asarray(ck.loops["kernels"][0], dtype=np.float64))
+    f32 = np_dtype_code(np.float32)
+
+    def both(run):
+        got = run()
+        served = dev.lib.cs_last_kernel(dev.ctx)
+        monkeypatch.setenv("CHROMOSIGHT_HIP_NO_SMALL_KEEP", "1")
+        dev_form = run()
+        monkeypatch.delenv("CHROMOSIGHT_HIP_NO_SMALL_KEEP")
+        assert served == dev.lib.cs_last_kernel(dev.ctx) == 5           # the masked matrix-core tile kernel, in both flows
+        assert _same(got, dev_form)
+        return got
+
+    # ---- 1: default == device keep, whole map and a row window; row-major as returned
+    n, md = 600, 150
+    band, bw, ld, miss = _noise_band(n, md, 177)
+    d_sig, d_miss = dev.to_device(band), dev.to_device(miss)
+    sig = CsMatrix(d_sig.ptr, f32, LAYOUT_BAND, ld, 0, bw)
+    kw = dict(pearson=0.25, lo_diag=0, hi_diag=md, inter=False, full=True, sym_upper=True, max_dist=md, mask_mode=MASK_BINS,
+              miss_row=d_miss, miss_col=d_miss, missing_tol=0.5, precision="f32")
+    for window in ((0, n), (137, 451)):
+        got = both(lambda: engine.run_candidates(dev, sig, (n, n), kspec, window, **kw))
+        assert len(got[0]) > 10 and np.all((got[0] >= window[0]) & (got[0] < window[1])) and np.all(got[2] >= 0.25)
+        assert np.array_equal(np.lexsort((got[1], got[0])), np.arange(len(got[0])))
+    # ---- 2: a list longer than the 8192 heads of the one launch, above LOW_PEARSON_F64 (float32 path)
+    n = 1500
+    band, bw, ld, miss = _noise_band(n, md, 177)
+    d_sig, d_miss = dev.to_device(band), dev.to_device(miss)
+    sig = CsMatrix(d_sig.ptr, f32, LAYOUT_BAND, ld, 0, bw)
+    kw.update(miss_row=d_miss, miss_col=d_miss)
+    for window in ((0, n), (137, 1351)):
+        for kw["pearson"] in (0.2, 0.16, 0.13, 0.115, 0.105):
+            assert kw["pearson"] > engine.LOW_PEARSON_F64
+            long_list = engine.run_candidates(dev, sig, (n, n), kspec, window, **kw)
+            if len(long_list[0]) > 8192:
+                break
+        print(f"window {window}: {len(long_list[0])} candidates at pearson {kw['pearson']}")
+        assert dev.lib.cs_last_kernel(dev.ctx) == 5 and 8192 < len(long_list[0]) < (1 << 16)
+        big = kw["pearson"]
+        kw["pearson"] = 0.6                                  # (a short list in between: the next call needs the second round)
+        assert len(engine.run_candidates(dev, sig, (n, n), kspec, window, **kw)[0]) < 2000
+        kw["pearson"] = big
+        for _ in range(2):
+            assert _same(long_list, engine.run_candidates(dev, sig, (n, n), kspec, window, **kw))
+        assert _same(long_list, both(lambda: engine.run_candidates(dev, sig, (n, n), kspec, window, **kw)))
+        assert np.array_equal(np.lexsort((long_list[1], long_list[0])), np.arange(len(long_list[0])))
+    # ---- 3: a tile list (dense, inter-like) is the call's own
+    rng = np.random.default_rng(178)
+    n_r, n_c = 300, 401
+    dense = (rng.gamma(3, 0.4, size=(n_r, n_c)) * (rng.random((n_r, n_c)) > 0.3)).astype(np.float32)
+    mr, mc = (rng.random(n_r) < 0.03).astype(np.uint8), (rng.random(n_c) < 0.03).astype(np.uint8)
+    dense[mr.astype(bool), :] = 0
+    dense[:, mc.astype(bool)] = 0
+    d_dense, ld = engine.to_device_map(dev, dense)
+    d_mr, d_mc = dev.to_device(mr), dev.to_device(mc)
+    sig = CsMatrix(d_dense.ptr, f32, LAYOUT_DENSE, ld, 0, 0)
+    kw = dict(pearson=0.15, lo_diag=-(n_r - 1), hi_diag=n_c - 1, inter=True, full=True, sym_upper=False, max_dist=None,
+              mask_mode=MASK_BINS, miss_row=d_mr, miss_col=d_mc, missing_tol=0.5, precision="f32")
+    for window in ((0, n_r), (37, 263)):
+        tiles_x, tiles_y = -(-n_c // 64), -(-(window[1] - window[0]) // 64)
+        every = np.arange(tiles_x * tiles_y, dtype=np.int32)
+        full = engine.run_candidates_tiles(dev, sig, (n_r, n_c), kspec, window, dev.to_device(every), every.size, **kw)
+        assert len(full[0]) > 50
+        half = engine.run_candidates_tiles(dev, sig, (n_r, n_c), kspec, window, dev.to_device(every[::2]), every[::2].size, **kw)
+        listed = np.isin((full[0] - window[0]) // 64 * tiles_x + full[1] // 64, every[::2])
+        assert 0 < listed.sum() < listed.size and _same(half, tuple(a[listed] for a in full))
+        assert _same(full, both(lambda: engine.run_candidates(dev, sig, (n_r, n_c), kspec, window, **kw)))
+
+
+# ------------------------------------------------------------------------------------------------
 # candidates per window + joint labelling == cs_detect_foci on the whole block
 # ------------------------------------------------------------------------------------------------
 def _genome(n=9000, seed=11):
