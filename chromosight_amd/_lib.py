@@ -271,6 +271,11 @@ _PROTOTYPES = {
                                  C.POINTER(C.c_int32)]),
     "cs_merge_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(CsCsr)), C.c_int32, C.POINTER(CsCsr)]),
     "cs_merge_tile_columns": (C.c_int32, []),
+    "cs_pairs_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "cs_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CsCsr)]),
+    "cs_pairs_block_pairs": (C.c_int32, []),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

@@ -235,3 +235,104 @@ def load_bed2d(path):
         bed.loc[flip, [s1, e1]] = b
         bed.loc[flip, [s2, e2]] = a
     return bed
+
+
+PAIRS_COLUMNS = ("chr1", "pos1", "chr2", "pos2")
+
+
+class PairsFile:
+    """A 4DN .pairs text file (plain or .gz) as a stream of chunks for cload.pairs_device: what read_pairs returns.  The header is
+    read when the object is made (`chromsizes`: the #chromsize: lines or the caller's; `columns`: the 0-based fields of chr1, pos1,
+    chr2, pos2); iterating reads the body, `chunk_rows` lines at a time, and yields (chrom1, pos1, chrom2, pos2) arrays: int32 ids
+    into `chromsizes` (-1: a name that is not in it) and int64 positions as the file has them (1-based in this format)."""
+
+    def __init__(self, path, chromsizes=None, chunk_rows=1 << 24):
+        if isinstance(chunk_rows, bool) or int(chunk_rows) != chunk_rows or int(chunk_rows) < 1:
+            raise ValueError(f"chunk_rows must be a positive integer, got {chunk_rows!r}")
+        self.path = os.fspath(path)
+        self.chunk_rows = int(chunk_rows)
+        header_sizes, columns, self.header_lines, self.width = {}, None, 0, 0
+        with self._open() as handle:
+            for line in handle:
+                if not line.startswith("#"):
+                    self.width = len(line.rstrip("\r\n").split("\t")) if line.strip() else 0
+                    break
+                self.header_lines += 1
+                fields = line.split()
+                if fields and fields[0] == "#chromsize:":
+                    if len(fields) != 3:
+                        raise ValueError(f"{self.path}, line {self.header_lines}: a #chromsize: line holds a name and a length")
+                    header_sizes[fields[1]] = int(fields[2])
+                elif fields and fields[0] == "#columns:":
+                    columns = fields[1:]
+        if columns is None:
+            self.columns = (1, 2, 3, 4)             # readID chr1 pos1 chr2 pos2 ...: fields 2 to 5
+        else:
+            missing = [name for name in PAIRS_COLUMNS if name not in columns]
+            if missing:
+                raise ValueError(f"{self.path}: the #columns: line names no {', '.join(missing)}")
+            self.columns = tuple(columns.index(name) for name in PAIRS_COLUMNS)
+        if chromsizes is None:
+            if not header_sizes:
+                raise ValueError(f"{self.path} has no #chromsize: lines: pass chromsizes")
+            chromsizes = header_sizes
+        items = list(chromsizes.items()) if hasattr(chromsizes, "items") else [tuple(x) for x in chromsizes]
+        self.chromsizes = {str(name): int(length) for name, length in items}
+
+    def _open(self):
+        if self.path.endswith(".gz"):
+            import gzip
+            return gzip.open(self.path, "rt")
+        return open(self.path, "rt")
+
+    def _short_line(self):
+        """ValueError for the first body line with too few fields (a walk in Python: only on the way to an error), or None."""
+        need = max(self.columns) + 1
+        with self._open() as handle:
+            for k, line in enumerate(handle):
+                if k >= self.header_lines and len(line.rstrip("\r\n").split("\t")) < need:
+                    return ValueError(f"{self.path}, line {k + 1}: too few fields for the columns {', '.join(PAIRS_COLUMNS)}")
+        return None
+
+    def __iter__(self):
+        import pandas as pd
+        if self.width <= max(self.columns):                   # the first body line is short, or there is no body
+            error = self._short_line()
+            if error is not None:
+                raise error
+            return
+        names = list(self.chromsizes)
+        line = self.header_lines                              # lines in front of the chunk at hand
+        with self._open() as handle:
+            reader = pd.read_csv(handle, sep="\t", header=None, names=list(range(self.width)), usecols=sorted(set(self.columns)),
+                                 skiprows=self.header_lines, dtype=str, na_filter=False, skip_blank_lines=False, comment=None,
+                                 quoting=csv.QUOTE_NONE, chunksize=self.chunk_rows)
+            while True:
+                try:
+                    frame = next(reader)
+                except StopIteration:
+                    return
+                except pd.errors.ParserError:                 # (a chunk of short lines only, for one)
+                    error = self._short_line()
+                    if error is None:
+                        raise
+                    raise error from None
+                cols = [frame[c].to_numpy() for c in self.columns]
+                if any((col == "").any() for col in cols):
+                    raise self._short_line() or ValueError(f"{self.path}, lines {line + 1} to {line + len(frame)}: an empty field")
+                ids = [pd.Categorical(cols[k], categories=names).codes.astype(np.int32) for k in (0, 2)]
+                try:
+                    pos = [cols[k].astype(np.int64) for k in (1, 3)]
+                except (ValueError, OverflowError):
+                    raise ValueError(f"{self.path}, lines {line + 1} to {line + len(frame)}: a position that is not an integer") from None
+                line += len(frame)
+                yield ids[0], pos[0], ids[1], pos[1]
+
+
+def read_pairs(path, chromsizes=None, chunk_rows=1 << 24):
+    """A host reader of the 4DN .pairs text format (what pairtools writes), plain or .gz: a PairsFile.  #chromsize: header lines
+    give `chromsizes` when the caller passes none (ValueError when there are none either); a #columns: line locates chr1 / pos1 /
+    chr2 / pos2 (default: fields 2 to 5); the body is tab-separated.  Iterating yields chunks of at most `chunk_rows` pairs as
+    (chrom1, pos1, chrom2, pos2) arrays with the names mapped to ids on the host, -1 for a name that is not in `chromsizes`.  A
+    line with too few fields raises ValueError with its line number."""
+    return PairsFile(path, chromsizes, chunk_rows)

@@ -477,6 +477,18 @@ class DeviceCool:
         self._init_resident(weight)
         return self
 
+    @classmethod
+    def from_pairs(cls, chunks, chromsizes, binsize, zero_based=False, dev=None):
+        """A DeviceCool binned on the device from read pairs (chromosight_amd/cload.py, cs_pairs_count / cs_pairs_fill): what
+        `cooler cload pairs` writes.  chunks: an iterable of (chrom1 id, pos1, chrom2 id, pos2) tuples of arrays (io.read_pairs
+        yields them), or one such tuple; chromsizes: ordered name -> length in bp; binsize in bp; positions are 1-based unless
+        zero_based.  Pairs with an id of -1 are dropped and counted in `.dropped`; ids or positions outside the genome refuse
+        the call (ValueError).  Every pixel lies on or above the diagonal; the counts are exact, so the table is bitwise the same
+        for every order of the pairs and every split into chunks.  The result has no weights: balance it (balance.ice_balance +
+        set_weights, or pipeline.open_pairs)."""
+        from .cload import pairs_device
+        return pairs_device(chunks, chromsizes, binsize, zero_based=zero_based, dev=dev)
+
     def _init_resident(self, weight):
         self._host_weight = None
         self._retired = []
@@ -1389,6 +1401,32 @@ def sub_matrices(dcool, inter):
     return [(a, b) for a in range(dcool.n_chrom) for b in range(dcool.n_chrom) if a == b or (a < b and inter)]
 
 
+def _resolution_factor(resolution, binsize):
+    """open_cool / open_pairs: the coarsening factor of `resolution` (None: 1) over a table of `binsize` bp."""
+    if resolution is None:
+        return 1
+    if isinstance(resolution, bool) or int(resolution) != resolution or resolution <= 0 or int(resolution) % binsize:
+        raise ValueError(f"resolution {resolution} is not a positive multiple of the file's bin size {binsize}")
+    return int(resolution) // binsize
+
+
+def _raw_weights(w):
+    return np.where(np.isfinite(np.asarray(w, dtype=np.float64)), 1.0, np.nan)
+
+
+def _coarsen_and_balance(dcool, factor, balance, norm, inter, n_mads):
+    """The tail open_cool and open_pairs share: coarsen the resident table by `factor` (> 1), then, for a table that counts as one
+    without stored weights (`balance`), ICE on the device with the reference's arguments -- the weights themselves, or 1.0 / NaN on
+    its detectable bins for norm="raw"."""
+    if factor > 1:
+        dcool = dcool.coarsened(factor)
+    if balance:
+        from .balance import ice_balance
+        weight, _ = ice_balance(dcool, cis_only=not inter, mad_max=n_mads, ignore_diags=2, min_nnz=10, max_iters=200)
+        dcool.set_weights(_raw_weights(weight) if norm == "raw" else weight)
+    return dcool
+
+
 def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None, resolution=None):
     """A .cool (path, `file.mcool::/resolutions/<binsize>`, or a decoded dictionary) resident on the device with the
     weights the reference's HicGenome.normalize gives it (contacts_map.py:182-229):
@@ -1431,15 +1469,10 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
     else:
         cools = [read(uri_or_cool)]
     cool = cools[0]
-    factor = 1
-    if resolution is not None:
-        binsize = int(cool["binsize"])
-        if isinstance(resolution, bool) or int(resolution) != resolution or resolution <= 0 or int(resolution) % binsize:
-            raise ValueError(f"resolution {resolution} is not a positive multiple of the file's bin size {binsize}")
-        factor = int(resolution) // binsize
+    factor = _resolution_factor(resolution, int(cool["binsize"]))
     # a coarsened table has no stored weights (the fine bins' mean nothing for the coarse ones), nor has a merged one
     weight = None if norm == "force" or factor > 1 or len(cools) > 1 else cool.get("weight")
-    raw = (lambda w: np.where(np.isfinite(np.asarray(w, dtype=np.float64)), 1.0, np.nan)) if norm == "raw" else (lambda w: w)
+    raw = _raw_weights if norm == "raw" else (lambda w: w)
     if len(cools) > 1:
         parts = []
         while cools:
@@ -1452,12 +1485,34 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
     else:
         cool["weight"] = None if weight is None else raw(weight)
         dcool = DeviceCool(cool, dev)
-    if factor > 1:
-        dcool = dcool.coarsened(factor)
-    if weight is None:
-        from .balance import ice_balance
-        weight, _ = ice_balance(dcool, cis_only=not inter, mad_max=n_mads, ignore_diags=2, min_nnz=10, max_iters=200)
-        dcool.set_weights(raw(weight))
+    return _coarsen_and_balance(dcool, factor, weight is None, norm, inter, n_mads)
+
+
+def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, norm="auto", inter=False, n_mads=5, dev=None,
+               resolution=None):
+    """Read pairs (a 4DN .pairs / .pairs.gz path, or an iterable of (chrom1, pos1, chrom2, pos2) chunks of arrays as
+    io.read_pairs yields them) binned at `binsize` bp on the device (DeviceCool.from_pairs: what `cooler cload pairs` writes, which
+    the reference expects to have been run beforehand) and given weights as open_cool gives them to a file without stored ones:
+    ICE on the device for norm="auto" and "force", its detectable bins with weights 1.0 / NaN for "raw".  chromsizes: ordered
+    name -> length in bp; None takes the #chromsize: lines of the file (a path only).  zero_based: the positions are taken as they
+    are instead of 1-based.  resolution: None, or a positive multiple of `binsize` to coarsen the binned table to first, as in
+    open_cool.  `.dropped` is the number of pairs left out for a chromosome that is not in `chromsizes`.  The binning is exact, so
+    every rank of a parallel run that bins its own copy gets the same table and weights."""
+    if norm not in ("auto", "raw", "force"):
+        raise ValueError("norm must be one of: auto, raw, force")
+    geometry_binsize = int(binsize)
+    factor = _resolution_factor(resolution, geometry_binsize)
+    chunks = path_or_chunks
+    if isinstance(chunks, (str, bytes)) or hasattr(chunks, "__fspath__"):
+        from . import io as cio
+        chunks = cio.read_pairs(chunks, chromsizes)
+        chromsizes = chunks.chromsizes
+    elif chromsizes is None:
+        raise ValueError("open_pairs needs chromsizes for pairs that do not come from a file")
+    dcool = DeviceCool.from_pairs(chunks, chromsizes, geometry_binsize, zero_based=zero_based, dev=dev)
+    dropped = dcool.dropped
+    dcool = _coarsen_and_balance(dcool, factor, True, norm, inter, n_mads)
+    dcool.dropped = dropped
     return dcool
 
 

@@ -458,6 +458,32 @@ int cs_merge_count(cs_ctx* ctx, void* stream, const cs_csr* const* tables, int32
 int cs_merge_fill(cs_ctx* ctx, void* stream, const cs_csr* const* tables, int32_t n_tables, cs_csr* out);
 int32_t cs_merge_tile_columns(void);
 
+/* ---- binning of read pairs into a pixel table: what `cooler cload pairs` writes (the first step of the chain that the reference
+ * leaves to cooler, before chromosight is started) ----
+ * A chunk is n_pairs (< 2^31 - 1; more: CS_ERR_UNSUPPORTED) pairs in four device columns: chromosome ids (int32 indices into the
+ * genome's chromosomes, -1 = a chromosome that is not part of it) and positions (int64, 1-based unless zero_based).  The genome is
+ * given on the host: h_chrom_lengths (n_chrom values >= 1, in bp), binsize (>= 1) and h_chrom_offsets (n_chrom + 1 values, the
+ * prefix sum of ceil(length / binsize), checked; 2^31 bins or more: CS_ERR_UNSUPPORTED).  A side with id -1 drops its pair; a side
+ * with an id outside [-1, n_chrom), or of a known chromosome with a zero-based position outside [0, length), refuses the chunk
+ * (CS_ERR_INVALID; cs_last_error names the number of refused pairs and the index of the first; a side that refuses counts before a
+ * side that drops).  The genome bin of a side is chrom_offset[c] + pos0 / binsize, a pair whose bin1 > bin2 is reflected, and the
+ * table holds one pixel per distinct (bin1, bin2), its count the number of pairs there, rows sorted by column.  Counts are exact
+ * integers: the table is bitwise the same for every order of the pairs, launch shape, context and device (integer atomics only).
+ * cs_pairs_count writes the sorted packed keys (bin1 << b | bin2, b = bits(n_bins - 1); dropped pairs last) to d_keys (n_pairs
+ *   entries) and the n_bins + 1 row pointers to d_out_indptr, and reports the number of pixels, the dtype of the counts (CS_F32 when
+ *   every count is below 2^24, else CS_F64) and the number of dropped pairs.  An empty chunk: zero row pointers, 0 pixels, no launch.
+ * cs_pairs_fill takes d_keys as cs_pairs_count left them and `out` with n_rows = n_cols = n_bins, d_indptr as cs_pairs_count wrote
+ *   it, nnz and dtype as it reported them and d_indices / d_data of exactly nnz entries of that dtype (row pointers or keys that do
+ *   not hold out->nnz pixels: CS_ERR_INVALID), and writes column bins and counts.  No store goes beyond out->nnz entries.
+ * cs_pairs_block_pairs: the sorted pairs one workgroup covers when the runs of equal keys are measured (tests and documents).
+ * Both calls are synchronous; the input columns are never written. */
+int cs_pairs_count(cs_ctx* ctx, void* stream, const int32_t* d_chrom1, const int64_t* d_pos1, const int32_t* d_chrom2,
+                   const int64_t* d_pos2, int64_t n_pairs, const int64_t* h_chrom_offsets, const int64_t* h_chrom_lengths,
+                   int32_t n_chrom, int64_t binsize, int32_t zero_based, int64_t* d_keys, int64_t* d_out_indptr, int64_t* h_out_nnz,
+                   int32_t* h_out_dtype, int64_t* h_out_dropped);
+int cs_pairs_fill(cs_ctx* ctx, void* stream, const int64_t* d_keys, int64_t n_pairs, cs_csr* out);
+int32_t cs_pairs_block_pairs(void);
+
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
     double pearson;         /* candidate threshold: coefficient >= pearson and != 0 (detection.py:417-421) */
