@@ -168,6 +168,19 @@ class CsSubsampleBlock(C.Structure):
     ]
 
 
+class CsTableReport(C.Structure):
+    """cs_table_report: what cs_table_from_columns_count says about a pixel table."""
+    _fields_ = [
+        ("nnz", C.c_int64),
+        ("count_min", C.c_int64),
+        ("count_max", C.c_int64),
+        ("ids_ok", C.c_int32),
+        ("sorted", C.c_int32),
+        ("upper", C.c_int32),
+        ("dtype", C.c_int32),
+    ]
+
+
 class CsCall(C.Structure):
     """One entry of a cs_run_calls list (include/chromosight_hip.h)."""
     _fields_ = [
@@ -276,6 +289,13 @@ _PROTOTYPES = {
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "cs_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CsCsr)]),
     "cs_pairs_block_pairs": (C.c_int32, []),
+    "cs_inflate_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                    C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "cs_inflate_max_chunk_bytes": (C.c_int64, []),
+    "cs_table_from_columns_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(CsTableReport)]),
+    "cs_table_from_columns_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32]),
     "cs_detect_foci": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(CsMatrix), C.POINTER(CsKernel),
                                  C.POINTER(CsNormxcorr2Params), C.POINTER(CsFociParams), C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p]),

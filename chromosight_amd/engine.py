@@ -506,6 +506,105 @@ def run_pileup_blocks(dev, blocks, kshape, blk, rows, cols, stream=None):
     return total, count
 
 
+# ------------------------------------------------------------------------------------------------
+# a .cool's pixel columns decoded on the device (cs_inflate.hip)
+# ------------------------------------------------------------------------------------------------
+CS_ERR_CORRUPT = -6
+INFLATE_STATUS = ("ok", "bad zlib header", "reserved block type", "stored block whose lengths disagree", "bad code set or code",
+                  "distance before the start of the output", "more output than the chunk holds", "less output than the chunk holds",
+                  "input exhausted", "Adler-32 mismatch", "unfiltered chunk of the wrong size")
+GATHER_SLACK = 2            # run_inflate_chunks copies the span that covers the chunks unless it is this many times their sum
+
+
+class CorruptChunks(ValueError):
+    """Chunks of a dataset that did not decode (cs_inflate_chunks returned CS_ERR_CORRUPT): .status holds the per-chunk codes
+    (indices into INFLATE_STATUS).  Every other chunk is in the column."""
+
+    def __init__(self, message, status):
+        super().__init__(message)
+        self.status = status
+
+
+def inflate_max_chunk_bytes():
+    """The largest decoded chunk cs_inflate_chunks takes (cs_inflate_max_chunk_bytes; no GPU needed)."""
+    return int(_lib.load_library().cs_inflate_max_chunk_bytes())
+
+
+@_one_call_per_context
+def run_inflate_chunks(dev, buf, index, out=None, stream=None):
+    """Decode the chunks of one dataset on the device (cs_inflate_chunks).  buf: the file, anything with the buffer protocol (a
+    mapping, bytes); index: its hdf5_lite.ChunkIndex (offsets into `buf`).  The bytes reach the device in one copy of the span that
+    covers the chunks, or, where that span is more than GATHER_SLACK times their sum (a file whose columns interleave), gathered
+    chunk by chunk into one staging array first.  Returns (column, status): a DeviceBuffer of index.length elements of
+    index.dtype (`out` when given) and the per-chunk status codes.  ValueError for a chunk that leaves `buf` or the column,
+    NotImplementedError beyond the limits of the kernel (element size, filters, chunk size), CorruptChunks when chunks failed."""
+    n = int(index.offsets.size)
+    offsets = np.ascontiguousarray(index.offsets, dtype=np.int64)
+    nbytes = np.ascontiguousarray(index.nbytes, dtype=np.int64)
+    starts = np.ascontiguousarray(index.starts, dtype=np.int64)
+    masks = np.ascontiguousarray(index.masks, dtype=np.uint32)
+    view = staged = None
+    try:                                            # (no view of `buf` outlives this block: a mapping with exported views cannot be closed)
+        view = np.frombuffer(buf, dtype=np.uint8)
+        if n and (offsets.min() < 0 or nbytes.min() < 0 or int((offsets + nbytes).max()) > view.size):
+            bad = int(np.argmax((offsets < 0) | (nbytes < 0) | (offsets + nbytes > view.size)))
+            raise ValueError(f"chunk {bad} (offset {int(offsets[bad])}, {int(nbytes[bad])} bytes) leaves the file of {view.size} bytes")
+        if n:
+            lo, hi = int(offsets.min()), int((offsets + nbytes).max())
+            total = int(nbytes.sum())
+            if hi - lo > GATHER_SLACK * max(total, 1):
+                staged = np.empty(total, dtype=np.uint8)
+                rel = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+                for o, k, a in zip(offsets.tolist(), nbytes.tolist(), rel.tolist()):
+                    staged[a:a + k] = view[o:o + k]
+            else:
+                staged, rel = view[lo:hi], offsets - lo
+            d_file = dev.to_device(staged, stream=stream)
+            file_bytes = int(staged.size)
+        else:
+            d_file, file_bytes, rel = None, 0, offsets
+    finally:
+        del view, staged
+    column = out if out is not None else dev.empty(max(int(index.length), 1), index.dtype)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    filters = np.asarray([fid for fid, _ in index.filters], dtype=np.int32)
+    rel = np.ascontiguousarray(rel, dtype=np.int64)
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))          # noqa: E731
+    rc = dev.lib.cs_inflate_chunks(dev.ctx, stream, d_file.ptr if d_file is not None else None, file_bytes, i64(rel), i64(nbytes), i64(starts),
+                                   masks.ctypes.data_as(C.POINTER(C.c_uint32)), n, int(index.dtype.itemsize), int(index.chunk),
+                                   int(index.length), filters.ctypes.data_as(C.POINTER(C.c_int32)), int(filters.size), column.ptr,
+                                   status.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc == CS_ERR_CORRUPT:
+        raise CorruptChunks(dev.lib.cs_last_error(dev.ctx).decode("utf-8", "replace"), status[:n])
+    dev._check(rc)
+    return column, status[:n]
+
+
+@_one_call_per_context
+def run_table_from_columns(dev, bin1, bin2, count, nnz, n_bins, stream=None):
+    """The finish pass over the decoded columns (cs_table_from_columns_count / _fill): bin1, bin2 (DeviceBuffers of int32 or int64, the
+    same for both) and count (int32 or int64), `nnz` pixels each.  Returns a dict: `indptr` (n_bins + 1 int64), `indices` (int32),
+    `data` (float32 when the largest count is below 2^24, else float64; exactly nnz entries, one when there is none), `nnz`,
+    `val_dtype`, `ids_ok`, `sorted`, `upper`, `count_min`, `count_max`.  A table that is not ids_ok and sorted comes back with `data`
+    None and row pointers that mean nothing."""
+    nnz, n_bins = int(nnz), int(n_bins)
+    if bin1.dtype != bin2.dtype or bin1.dtype not in (np.dtype(np.int32), np.dtype(np.int64)) or \
+            count.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise NotImplementedError(f"pixel columns of {bin1.dtype} / {bin2.dtype} / {count.dtype}: int32 or int64 ids and counts only")
+    indptr = dev.empty(n_bins + 1, np.int64)
+    indices = dev.empty(max(nnz, 1), np.int32)
+    rep = _lib.CsTableReport()
+    dev._check(dev.lib.cs_table_from_columns_count(dev.ctx, stream, bin1.ptr, bin2.ptr, bin1.dtype.itemsize, count.ptr, count.dtype.itemsize, nnz,
+                                                   n_bins, indptr.ptr, indices.ptr, C.byref(rep)))
+    val_dtype = np.float32 if rep.dtype == CS_F32 else np.float64
+    out = {"indptr": indptr, "indices": indices, "data": None, "nnz": nnz, "val_dtype": val_dtype, "ids_ok": bool(rep.ids_ok),
+           "sorted": bool(rep.sorted), "upper": bool(rep.upper), "count_min": int(rep.count_min), "count_max": int(rep.count_max)}
+    if out["ids_ok"] and out["sorted"]:
+        out["data"] = dev.empty(max(nnz, 1), val_dtype)
+        dev._check(dev.lib.cs_table_from_columns_fill(dev.ctx, stream, count.ptr, count.dtype.itemsize, nnz, out["data"].ptr, int(rep.dtype)))
+    return out
+
+
 def pileup_chunk(n):
     """Positions per chunk of the pileup's summation order for n positions (cs_pileup_chunk; no GPU needed)."""
     return int(_lib.load_library().cs_pileup_chunk(int(n)))

@@ -13,10 +13,23 @@ Neither cooler nor h5py exists in the target image; the reference reads the same
 import mmap
 import struct
 import zlib
+from typing import NamedTuple
 
 import numpy as np
 
 UNDEF = 0xFFFFFFFFFFFFFFFF
+
+
+class ChunkIndex(NamedTuple):
+    """Where the chunks of a chunked 1-D dataset lie in the file (File.chunk_index)."""
+    dtype: np.dtype
+    length: int                 # elements of the dataset
+    chunk: int                  # elements of a chunk (the last one is padded in the file)
+    filters: tuple              # ((filter id, client data), ...) in pipeline order
+    offsets: np.ndarray         # int64, per chunk: file offset of the stored bytes
+    nbytes: np.ndarray          # int64: their number
+    starts: np.ndarray          # int64: the chunk's first element
+    masks: np.ndarray           # uint32: bit k set = filter k was not applied to this chunk
 
 
 class Hdf5Unsupported(Exception):
@@ -249,6 +262,50 @@ class File:
                 q += key + 8
         walk(btree)
         return out
+
+    def chunk_index(self, path):
+        """The ChunkIndex of a chunked 1-D dataset, its chunks in the order dataset() visits them; nothing is decoded.  A node of
+        the chunk B-tree is parsed as one array of records, not entry by entry.  Any other layout: Hdf5Unsupported."""
+        msgs = self.messages(self.resolve(path))
+        dt = shape = layout = None
+        filters = []
+        for t, d in msgs:
+            if t == 0x03:
+                dt, _ = self._dtype(d)
+            elif t == 0x01:
+                shape = self._shape(d)
+            elif t == 0x08:
+                layout = d
+            elif t == 0x0B:
+                filters = self._filters(d)
+        if dt is None or shape is None or layout is None or len(shape) != 1:
+            raise Hdf5Unsupported(f"{path}: not a 1-D dataset")
+        if layout[0] != 3 or layout[1] != 2:
+            raise Hdf5Unsupported(f"{path}: not a chunked dataset (layout version {layout[0]}, class {layout[1]})")
+        rank = layout[2]                                 # dataset rank + 1
+        btree, = struct.unpack_from("<Q", layout, 3)
+        chunk = struct.unpack_from(f"<{rank}I", layout, 11)[0]
+        entry = np.dtype([("nbytes", "<u4"), ("mask", "<u4"), ("start", "<u8"), ("rest", f"V{8 * (rank - 1)}"), ("child", "<u8")])
+        b = self.buf
+        leaves = []
+
+        def walk(node):
+            p = self.base + node
+            if b[p:p + 4] != b"TREE" or b[p + 4] != 1:
+                raise Hdf5Unsupported("bad chunk B-tree")
+            level, n_ent = b[p + 5], struct.unpack_from("<H", b, p + 6)[0]
+            entries = np.frombuffer(b[p + 24:p + 24 + n_ent * entry.itemsize], dtype=entry)      # (a copy: the slice of a mapping is bytes)
+            if level:
+                for child in entries["child"].tolist():
+                    walk(child)
+            else:
+                leaves.append(entries)
+        if btree != UNDEF:
+            walk(btree)
+        # (copies: nothing refers to the mapping once this returns)
+        col = lambda name, dtype: np.concatenate([e[name] for e in leaves]).astype(dtype) if leaves else np.zeros(0, dtype=dtype)  # noqa: E731
+        return ChunkIndex(dt, int(shape[0]), int(chunk), tuple(filters), col("child", np.int64) + np.int64(self.base), col("nbytes", np.int64),
+                          col("start", np.int64), col("mask", np.uint32))
 
     @staticmethod
     def _filters(data):

@@ -90,16 +90,14 @@ def _load_cool_native(path, group, balance, norm):
         return _read_cool_datasets(f, path, group, balance, norm)
 
 
-def _read_cool_datasets(f, path, group, balance, norm):
+def _read_cool_geometry(f, path, group, balance, norm):
+    """Everything of a .cool but its pixel table: names, offsets, bin starts / ends, bin size and the weights under _weights' rules."""
     ds = lambda name: f"{group}/{name}"
     names = f.dataset(ds("chroms/name"))
     attrs = f.attrs(group or "/")
     if "bin-size" not in attrs:
         raise hdf5_lite.Hdf5Unsupported("no numeric bin-size attribute (variable-size bins?)")
     cool = {
-        "bin1_id": f.dataset(ds("pixels/bin1_id")),
-        "bin2_id": f.dataset(ds("pixels/bin2_id")),
-        "count": f.dataset(ds("pixels/count")),
         "bin_start": f.dataset(ds("bins/start")).astype(np.int64),
         "bin_end": f.dataset(ds("bins/end")).astype(np.int64),
         "chrom_offset": f.dataset(ds("indexes/chrom_offset")).astype(np.int64),
@@ -108,6 +106,17 @@ def _read_cool_datasets(f, path, group, balance, norm):
     }
     cool["weight"] = _weights(path, balance, norm, cool["bin_start"].size,
                               lambda: f.dataset(ds(f"bins/{balance}")) if f.exists(ds(f"bins/{balance}")) else None)
+    return cool
+
+
+def _read_cool_datasets(f, path, group, balance, norm):
+    ds = lambda name: f"{group}/{name}"
+    cool = {
+        "bin1_id": f.dataset(ds("pixels/bin1_id")),
+        "bin2_id": f.dataset(ds("pixels/bin2_id")),
+        "count": f.dataset(ds("pixels/count")),
+    }
+    cool.update(_read_cool_geometry(f, path, group, balance, norm))
     return cool
 
 
@@ -162,9 +171,14 @@ def _read_cool(uri, balance="weight"):
     return _load(uri, balance, None)
 
 
-def _load(uri, balance, norm):
+def split_uri(uri):
+    """(path, group) of `file.cool` or `file.mcool::/resolutions/<binsize>`."""
     path, _, group = str(uri).partition("::")
-    group = "/" + group.strip("/") if group else ""
+    return path, "/" + group.strip("/") if group else ""
+
+
+def _load(uri, balance, norm):
+    path, group = split_uri(uri)
     cool = None
     if not os.environ.get("CHROMOSIGHT_H5DUMP_ONLY"):
         try:

@@ -404,6 +404,8 @@ class DeviceCool:
     contacts_map.py:531), the slicing of the block, diag_trim, the distance law, detrend and the
     band tiler all read the same arrays (cs_csr views, include/chromosight_hip.h)."""
 
+    _host_dtypes = (np.int64, np.int64, np.int64)      # of bin1_id, bin2_id, count in a `.host` that is downloaded
+
     def __init__(self, cool, dev=None):
         if isinstance(cool, (str, bytes)) or hasattr(cool, "__fspath__"):
             from . import io as cio
@@ -489,6 +491,19 @@ class DeviceCool:
         from .cload import pairs_device
         return pairs_device(chunks, chromsizes, binsize, zero_based=zero_based, dev=dev)
 
+    @classmethod
+    def from_cool_file(cls, path, *, balance="weight", dev=None):
+        """A DeviceCool whose pixel table was decoded on the device (cs_inflate_chunks, cs_table_from_columns_*): the stored chunks
+        of pixels/bin1_id, bin2_id and count go to HBM as they are in the file, are inflated and unshuffled there, and one pass
+        checks the table and builds what the constructor would upload for the same file -- row pointers, int32 column bins, counts
+        as float32 or float64 -- bit for bit.  path: a .cool, or `file.mcool::/resolutions/<binsize>`.  The small datasets
+        (chromosome names and offsets, bin starts and ends, the `bins/<balance>` column, taken as stored; a file without one gives a
+        table without weights) are decoded on the host.  `.host` is downloaded when first read.  DeviceDecodeRefused (a ValueError)
+        for a file that does not qualify: one hdf5_lite does not read, pixel columns that are not chunked int32 / int64 datasets with
+        filters among shuffle, gzip and Fletcher-32 in that order, chunks beyond engine.inflate_max_chunk_bytes(), ids outside the
+        bins, or a table that is not strictly sorted by (bin1, bin2).  engine.CorruptChunks for chunks that do not decode."""
+        return _device_cool_from_file(path, balance, dev, lambda cool: cool["weight"])
+
     def _init_resident(self, weight):
         self._host_weight = None
         self._retired = []
@@ -528,13 +543,14 @@ class DeviceCool:
     @property
     def host(self):
         """The pixel table as a decoded-cool dictionary (bin1_id, bin2_id, count, weight, ...).  A table built on the device
-        (from_device_csr) downloads it here, once."""
+        (from_device_csr, from_cool_file) downloads it here, once; one decoded from a file gets the dtypes io._read_cool gives."""
         if self._host is None:
             n = int(self.nnz)
             indptr = self.indptr.download()
-            b1 = np.repeat(np.arange(self.n_bins, dtype=np.int64), np.diff(indptr))
-            b2 = self.indices.download()[:n].astype(np.int64)
-            cnt = self.data.download().view(self.val_dtype)[:n].astype(np.int64)
+            t1, t2, tc = self._host_dtypes
+            b1 = np.repeat(np.arange(self.n_bins, dtype=t1), np.diff(indptr))
+            b2 = self.indices.download()[:n].astype(t2)
+            cnt = self.data.download().view(self.val_dtype)[:n].astype(tc)
             self._host = {"binsize": self.binsize, "chrom_offset": self.offsets, "chrom_names": np.asarray(self.names), "bin1_id": b1,
                           "bin2_id": b2, "count": cnt, "weight": self._host_weight, "bin_start": self.bin_start,
                           "bin_end": self.bin_end}
@@ -1427,7 +1443,107 @@ def _coarsen_and_balance(dcool, factor, balance, norm, inter, n_mads):
     return dcool
 
 
-def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None, resolution=None):
+def _is_path(source):
+    return isinstance(source, (str, bytes)) or hasattr(source, "__fspath__")
+
+
+class DeviceDecodeRefused(ValueError):
+    """The file does not qualify for the device decode (DeviceCool.from_cool_file, open_cool(decode="device"))."""
+
+
+AUTO_DECODE_ON_DEVICE = True        # what open_cool(decode="auto") does with a file that qualifies (tools/time_cool_decode.py)
+_PIXEL_COLUMNS = ("bin1_id", "bin2_id", "count")
+
+
+def _decode_route(decode):
+    """open_cool's `decode` under the environment: "auto", "host" or "device"."""
+    if decode not in ("auto", "host", "device"):
+        raise ValueError("decode must be one of: auto, host, device")
+    if os.environ.get("CHROMOSIGHT_HIP_HOST_DECODE", "") not in ("", "0"):
+        if decode == "device":
+            raise ValueError("decode='device' while CHROMOSIGHT_HIP_HOST_DECODE forces the host route")
+        return "host"
+    return decode if decode != "auto" or AUTO_DECODE_ON_DEVICE else "host"
+
+
+def device_decode_refusal(indexes, max_chunk_bytes):
+    """Why the pixel columns of a file are not decoded on the device, or None when they are.  indexes: name -> hdf5_lite.ChunkIndex
+    of pixels/bin1_id, bin2_id and count (None: not a chunked dataset); max_chunk_bytes: engine.inflate_max_chunk_bytes()."""
+    for name in _PIXEL_COLUMNS:
+        idx = indexes.get(name)
+        if idx is None:
+            return f"pixels/{name} is not a chunked dataset"
+        if idx.dtype.kind != "i" or idx.dtype.itemsize not in (4, 8):
+            return f"pixels/{name} holds {idx.dtype}, not int32 or int64"
+        stage = 0
+        for fid, _ in idx.filters:
+            at = {2: 1, 1: 2, 3: 3}.get(int(fid), 0)
+            if at <= stage:
+                return f"pixels/{name} has filter {fid}" if at == 0 else f"pixels/{name} has its filters in another order than shuffle, gzip, Fletcher-32"
+            stage = at
+        if idx.chunk < 1 or idx.chunk * idx.dtype.itemsize > max_chunk_bytes:
+            return f"pixels/{name} has chunks of {idx.chunk * idx.dtype.itemsize} bytes, the device decodes up to {max_chunk_bytes}"
+    if indexes["bin1_id"].dtype != indexes["bin2_id"].dtype:
+        return "pixels/bin1_id and pixels/bin2_id differ in type"
+    if len({indexes[name].length for name in _PIXEL_COLUMNS}) != 1:
+        return "the pixel columns differ in length"
+    return None
+
+
+def _device_cool_from_file(uri, balance, dev, pick_weight):
+    """DeviceCool.from_cool_file; pick_weight(cool) -> the weights to set, from everything of the file but its pixels."""
+    from . import hdf5_lite, io as cio
+    path, group = cio.split_uri(uri)
+    if os.environ.get("CHROMOSIGHT_H5DUMP_ONLY"):
+        raise DeviceDecodeRefused(f"{uri}: CHROMOSIGHT_H5DUMP_ONLY sends every file through the HDF5 command line tool")
+    dev = dev or get_device()
+    try:
+        with hdf5_lite.File(path) as f:
+            indexes = {}
+            for name in _PIXEL_COLUMNS:
+                try:
+                    indexes[name] = f.chunk_index(f"{group}/pixels/{name}")
+                except hdf5_lite.Hdf5Unsupported:
+                    indexes[name] = None
+            reason = device_decode_refusal(indexes, engine.inflate_max_chunk_bytes())
+            if reason:
+                raise DeviceDecodeRefused(f"{uri}: {reason}")
+            cool = cio._read_cool_geometry(f, path, group, balance, None)
+            with dev.lock:
+                columns = {name: engine.run_inflate_chunks(dev, f.buf, indexes[name])[0] for name in _PIXEL_COLUMNS}
+    except hdf5_lite.Hdf5Unsupported as exc:
+        raise DeviceDecodeRefused(f"{uri}: {exc}") from None
+    except NotImplementedError as exc:              # CS_ERR_UNSUPPORTED: a limit of the kernel the rule above does not know
+        raise DeviceDecodeRefused(f"{uri}: {exc}") from None
+    off = np.asarray(cool["chrom_offset"], dtype=np.int64)
+    n_bins, nnz = int(off[-1]), int(indexes["count"].length)
+    with dev.lock:
+        res = engine.run_table_from_columns(dev, columns["bin1_id"], columns["bin2_id"], columns["count"], nnz, n_bins)
+    if not res["ids_ok"]:
+        raise DeviceDecodeRefused(f"{uri}: bin ids outside [0, {n_bins})")
+    if not res["sorted"]:
+        raise DeviceDecodeRefused(f"{uri}: the pixel table is not strictly sorted by (bin1, bin2)")
+    del columns
+    self = DeviceCool.__new__(DeviceCool)
+    self.dev = dev
+    self.offsets, self.n_bins = off, n_bins
+    self.names = [str(n) for n in cool["chrom_names"]]
+    self.binsize = int(cool["binsize"])
+    self.bin_start, self.bin_end = cool.get("bin_start"), cool.get("bin_end")
+    self.val_dtype = res["val_dtype"]
+    self._counts_exact = bool(self.val_dtype is np.float32 and (nnz == 0 or res["count_min"] >= 0))
+    self.nnz = nnz
+    self.indptr, self.indices, self.data = res["indptr"], res["indices"], res["data"]
+    self._host = None
+    # (io._load narrows the ids of a table that has pixels when all are below 2^31; here every id is below n_bins)
+    ids = np.int32 if nnz and n_bins <= 2 ** 31 else indexes["bin1_id"].dtype.type
+    self._host_dtypes = (ids, ids, indexes["count"].dtype.type)
+    self.upper = bool(res["upper"])
+    self._init_resident(pick_weight(cool))
+    return self
+
+
+def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None, resolution=None, decode="auto"):
     """A .cool (path, `file.mcool::/resolutions/<binsize>`, or a decoded dictionary) resident on the device with the
     weights the reference's HicGenome.normalize gives it (contacts_map.py:182-229):
 
@@ -1452,40 +1568,53 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
     writes, which the reference expects to have been run beforehand); the coarse table has no stored weights, so `norm` applies as
     to a file without any: ICE on the coarse table for "auto" and "force", its detectable bins with weights 1.0 / NaN for "raw".
     The file's own bin size: as without the argument.  Every rank of a parallel run that coarsens its own copy gets the same table
-    and weights."""
+    and weights.
+
+    decode: where the pixel columns of a file are decoded.  "auto": on the device (DeviceCool.from_cool_file) when the file
+    qualifies -- hdf5_lite reads it, its pixel columns are chunked int32 / int64 datasets with filters among shuffle, gzip and
+    Fletcher-32, no chunk decodes to more than engine.inflate_max_chunk_bytes(), and the table is strictly sorted -- and on the host,
+    as before, when it does not.  "host": always on the host; CHROMOSIGHT_HIP_HOST_DECODE=1 in the environment does the same.
+    "device": on the device, DeviceDecodeRefused (a ValueError) for a file that does not qualify and ValueError for a dictionary,
+    which is decoded already.  Both routes give the same table, bit for bit."""
     if norm not in ("auto", "raw", "force"):
         raise ValueError("norm must be one of: auto, raw, force")
-
-    def read(source):
-        if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
-            from . import io as cio
-            return cio._read_cool(source, balance)
-        return dict(source)
-
-    if isinstance(uri_or_cool, (list, tuple)):
-        if not uri_or_cool:
-            raise ValueError("open_cool got an empty list: at least one .cool is needed")
-        cools = [read(source) for source in uri_or_cool]
-    else:
-        cools = [read(uri_or_cool)]
-    cool = cools[0]
-    factor = _resolution_factor(resolution, int(cool["binsize"]))
-    # a coarsened table has no stored weights (the fine bins' mean nothing for the coarse ones), nor has a merged one
-    weight = None if norm == "force" or factor > 1 or len(cools) > 1 else cool.get("weight")
+    route = _decode_route(decode)
+    sources = list(uri_or_cool) if isinstance(uri_or_cool, (list, tuple)) else [uri_or_cool]
+    if not sources:
+        raise ValueError("open_cool got an empty list: at least one .cool is needed")
+    many = len(sources) > 1
     raw = _raw_weights if norm == "raw" else (lambda w: w)
-    if len(cools) > 1:
-        parts = []
-        while cools:
-            part = cools.pop(0)
-            part["weight"] = None
-            parts.append(DeviceCool(part, dev))
-        del part, cool
-        dcool = parts[0].merged(*parts[1:])
-        del parts                                   # the sources' HBM is released here
-    else:
-        cool["weight"] = None if weight is None else raw(weight)
-        dcool = DeviceCool(cool, dev)
-    return _coarsen_and_balance(dcool, factor, weight is None, norm, inter, n_mads)
+
+    def pick_weight(cool):
+        # a coarsened table has no stored weights (the fine bins' mean nothing for the coarse ones), nor has a merged one
+        factor = _resolution_factor(resolution, int(cool["binsize"]))
+        weight = None if norm == "force" or factor > 1 or many else cool.get("weight")
+        return None if weight is None else raw(weight)
+
+    def open_one(source):
+        if not _is_path(source):
+            if route == "device":
+                raise ValueError("decode='device' takes files: a dictionary is a decoded table already")
+            cool = dict(source)
+        else:
+            if route != "host":
+                try:
+                    return _device_cool_from_file(source, balance, dev, pick_weight)
+                except DeviceDecodeRefused:
+                    if route == "device":
+                        raise
+            from . import io as cio
+            cool = cio._read_cool(source, balance)
+        cool["weight"] = pick_weight(cool)
+        return DeviceCool(cool, dev)
+
+    parts = []
+    while sources:
+        parts.append(open_one(sources.pop(0)))          # (a source's host columns are released once it is uploaded)
+    dcool = parts[0].merged(*parts[1:]) if many else parts[0]
+    del parts                                       # the sources' HBM is released here
+    factor = _resolution_factor(resolution, dcool.binsize)
+    return _coarsen_and_balance(dcool, factor, many or not dcool.has_weights, norm, inter, n_mads)
 
 
 def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, norm="auto", inter=False, n_mads=5, dev=None,

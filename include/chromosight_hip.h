@@ -49,9 +49,10 @@ typedef enum {
     CS_ERR_HIP = -2,       /* HIP runtime error */
     CS_ERR_UNSUPPORTED = -3,
     CS_ERR_OVERFLOW = -4,  /* an output buffer was too small; see the call's doc */
-    CS_ERR_RANGE = -5      /* cs_normxcorr2_host, cs_normxcorr2 with cs_ctx_set_range_check: the map holds a non-finite pixel,
+    CS_ERR_RANGE = -5,     /* cs_normxcorr2_host, cs_normxcorr2 with cs_ctx_set_range_check: the map holds a non-finite pixel,
                               or magnitudes beyond what the float32 kernels square without overflow (1e15): evaluate it in
                               float64 (the Python shim does) */
+    CS_ERR_CORRUPT = -6    /* cs_inflate_chunks: at least one chunk of the file did not decode; see its per-chunk status */
 } cs_status;
 
 enum { CS_F32 = 0, CS_F64 = 1, CS_U8 = 2 /* masks only */ };
@@ -483,6 +484,47 @@ int cs_pairs_count(cs_ctx* ctx, void* stream, const int32_t* d_chrom1, const int
                    int32_t* h_out_dtype, int64_t* h_out_dropped);
 int cs_pairs_fill(cs_ctx* ctx, void* stream, const int64_t* d_keys, int64_t n_pairs, cs_csr* out);
 int32_t cs_pairs_block_pairs(void);
+
+/* ---- the pixel columns of a .cool decoded from file bytes in HBM: what the HDF5 library does for cooler on the host (chunks of a
+ * 1-D dataset through the filters shuffle, gzip and Fletcher-32), and what pipeline.DeviceCool's constructor makes of the three
+ * columns ----
+ * cs_inflate_chunks decodes n_chunks (< 2^31 - 1) stored chunks of one dataset into its column d_out (n_elems elements of elem_bytes
+ *   = 1, 2, 4 or 8 bytes; anything else: CS_ERR_UNSUPPORTED).  d_file: file_bytes bytes of the file (any span of it) on the device;
+ *   per chunk, host arrays of its offset in d_file, its stored size, its first element in the column and its filter mask (bit k set:
+ *   filter k of the list was not applied to this chunk).  chunk_elems: elements per chunk (the last chunk is padded in the file and
+ *   clipped to n_elems here: no store goes beyond the column); chunk_elems * elem_bytes above cs_inflate_max_chunk_bytes():
+ *   CS_ERR_UNSUPPORTED.  h_filters: the n_filters ids of the dataset's pipeline in the order they were applied when written, a
+ *   subsequence of shuffle (2), gzip (1), Fletcher-32 (3); another id or order: CS_ERR_UNSUPPORTED.  A Fletcher-32 checksum is cut
+ *   off, not verified.  A chunk whose bytes leave d_file or whose first element leaves the column: CS_ERR_INVALID, found on the host
+ *   before anything is launched.  h_status receives a code per chunk: 0, or 1 bad zlib header, 2 reserved block type, 3 stored block
+ *   whose lengths disagree, 4 bad code set or code, 5 distance before the start of the output, 6 more output than a chunk holds,
+ *   7 less, 8 input exhausted, 9 Adler-32 mismatch, 10 a chunk without gzip whose stored size is not a chunk's.  A failed chunk
+ *   writes nothing to d_out and stops no other chunk; when any failed the call returns CS_ERR_CORRUPT and cs_last_error names their
+ *   number and the first.  No stream can make the kernel read outside its chunk's bytes or write outside its chunk's elements.
+ * cs_inflate_max_chunk_bytes: the largest decoded chunk (128 KiB: a chunk is decoded in a CU's on-chip memory).
+ * cs_table_from_columns_count takes the decoded columns as stored -- bin1_id and bin2_id of id_bytes (4 or 8: int32 / int64), count of
+ *   count_bytes (4 or 8: int32 / int64), nnz pixels each -- and n_bins (< 2^31 - 1), and writes the n_bins + 1 row pointers
+ *   (searchsorted(bin1_id, 0 .. n_bins); the file's own index is not consulted) and the column bins as int32.  The report says whether
+ *   every id lies in [0, n_bins), whether the table is strictly sorted by (bin1, bin2), whether every pixel has bin2 >= bin1, the
+ *   smallest and largest count and the dtype of the counts (CS_F32 when the largest is below 2^24, else CS_F64).  Row pointers and
+ *   column bins mean nothing unless ids_ok and sorted.  Integer atomics only.
+ * cs_table_from_columns_fill writes the nnz counts as that dtype into d_out_data (exactly nnz entries).
+ * All are synchronous and never write their inputs. */
+typedef struct {
+    int64_t nnz;
+    int64_t count_min, count_max;       /* 0 for an empty table */
+    int32_t ids_ok, sorted, upper;
+    int32_t dtype;
+} cs_table_report;
+int cs_inflate_chunks(cs_ctx* ctx, void* stream, const void* d_file, int64_t file_bytes, const int64_t* h_offsets, const int64_t* h_nbytes,
+                      const int64_t* h_starts, const uint32_t* h_masks, int64_t n_chunks, int32_t elem_bytes, int64_t chunk_elems,
+                      int64_t n_elems, const int32_t* h_filters, int32_t n_filters, void* d_out, int32_t* h_status);
+int64_t cs_inflate_max_chunk_bytes(void);
+int cs_table_from_columns_count(cs_ctx* ctx, void* stream, const void* d_bin1, const void* d_bin2, int32_t id_bytes, const void* d_count,
+                                int32_t count_bytes, int64_t nnz, int64_t n_bins, int64_t* d_out_indptr, int32_t* d_out_indices,
+                                cs_table_report* h_report);
+int cs_table_from_columns_fill(cs_ctx* ctx, void* stream, const void* d_count, int32_t count_bytes, int64_t nnz, void* d_out_data,
+                               int32_t dtype);
 
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
