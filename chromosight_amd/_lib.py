@@ -181,6 +181,30 @@ class CsTableReport(C.Structure):
     ]
 
 
+class CsPairsTextFormat(C.Structure):
+    """cs_pairs_text_format: where the four columns stand in a line of a .pairs body, and the chromosome names."""
+    _fields_ = [
+        ("col_chrom1", C.c_int32),
+        ("col_pos1", C.c_int32),
+        ("col_chrom2", C.c_int32),
+        ("col_pos2", C.c_int32),
+        ("width", C.c_int32),
+        ("n_names", C.c_int32),
+        ("h_name_bytes", C.c_void_p),
+        ("h_name_offsets", C.c_void_p),
+    ]
+
+
+class CsPairsTextReport(C.Structure):
+    """cs_pairs_text_report: the lines of a text and the first flagged one."""
+    _fields_ = [
+        ("n_lines", C.c_int64),
+        ("first_flagged", C.c_int64),
+        ("reason", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class CsCall(C.Structure):
     """One entry of a cs_run_calls list (include/chromosight_hip.h)."""
     _fields_ = [
@@ -289,6 +313,12 @@ _PROTOTYPES = {
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "cs_pairs_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CsCsr)]),
     "cs_pairs_block_pairs": (C.c_int32, []),
+    "cs_pairs_text_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "cs_pairs_text_parse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CsPairsTextFormat), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(CsPairsTextReport)]),
+    "cs_pairs_text_tile_bytes": (C.c_int32, []),
+    "cs_pairs_text_max_line_bytes": (C.c_int32, []),
+    "cs_pairs_text_name_slot": (C.c_int32, [C.c_char_p, C.c_int64, C.c_int64]),
     "cs_inflate_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),

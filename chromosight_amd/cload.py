@@ -21,20 +21,34 @@ The reference runs on a finished .cool and leaves every step before it to cooler
 - sums are integers and exact: the table is bitwise the same for every order of the pairs, every split into chunks, and every
   launch shape, context and device (integer atomics only, no float atomics);
 - fewer than 2^31 - 1 pairs per chunk, fewer than 2^31 - 1 pixels in any table, fewer than 2^31 genome bins (ValueError beyond);
-- no weights are carried: the result is a table without weights, as a merged or coarsened one is."""
+- no weights are carried: the result is a table without weights, as a merged or coarsened one is.
+
+The text of a .pairs file becomes such columns on the device too (cs_pairs_text_count / cs_pairs_text_parse,
+chromosight_amd/csrc/cs_pairs_text.hip): parse_pairs_text for one piece of body text, pairs_file_device for a file, which is read
+in pieces cut at a line end (text_pieces), each parsed, binned and merged like a chunk above.  The device takes a strict subset of
+what io.PairsFile takes (include/chromosight_hip.h states it) and flags every other line, which then goes to the host reader."""
 import ctypes as C
+import zlib
 from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import CS_F32, CsCsr, get_device, load_library, np_dtype_code
+from ._lib import CS_F32, CsCsr, CsPairsTextFormat, CsPairsTextReport, DeviceBuffer, get_device, load_library, np_dtype_code
 
 MAX_CHUNK_PAIRS = 2 ** 31 - 2
+PIECE_BYTES = 1 << 27           # the text of a file that goes to the device at a time (pairs_file_device)
+FLAG_REASONS = {1: "an empty line", 2: "too few fields", 3: "too many fields", 4: "an empty name or position",
+                5: "a position that is not 1 to 18 digits", 6: "a carriage return that does not end the line", 7: "a NUL byte",
+                8: "a byte that is not ASCII", 9: "a line longer than the device takes"}
 
 
 def __getattr__(name):
     if name == "BLOCK_PAIRS":                   # the sorted pairs one workgroup of the run-length pass covers; read from the
         return int(load_library().cs_pairs_block_pairs())           # library when asked for, so that importing needs none
+    if name == "TEXT_TILE_BYTES":               # the text one workgroup of the parser covers
+        return int(load_library().cs_pairs_text_tile_bytes())
+    if name == "MAX_LINE_BYTES":                # the longest line the parser takes, without its terminator
+        return int(load_library().cs_pairs_text_max_line_bytes())
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -155,22 +169,250 @@ def pairs_device(chunks, chromsizes, binsize, zero_based=False, dev=None):
     after the columns and scratch are gone, the chunk's table + the running table + the merged result.
     The result has no weights, upper = True, the geometry's names, bin_start and bin_end, and `.dropped`: the pairs dropped for an
     id of -1, summed over the chunks.  ValueError as pairs_csr; the chunks before a refused one have been consumed."""
-    from .pipeline import DeviceCool
     dev = dev or get_device()
     geo = chromsizes if isinstance(chromsizes, Geometry) and int(binsize) == chromsizes.binsize else bin_geometry(chromsizes, binsize)
-    none = np.zeros(0, dtype=np.int64)
-    table = DeviceCool({"binsize": geo.binsize, "chrom_offset": geo.offsets, "chrom_names": np.asarray(geo.names, dtype=str), "bin1_id": none,
-                        "bin2_id": none, "count": none, "weight": None, "bin_start": geo.bin_start, "bin_end": geo.bin_end}, dev)
-    empty = table                                   # the parent from_device_csr wants: the geometry, no pixels, no weights
-    dropped = 0
+    running = _RunningTable(geo, dev)
     for chunk in ([chunks] if _is_single_chunk(chunks) else chunks):
         chrom1, pos1, chrom2, pos2 = chunk
-        res = pairs_csr(dev, geo, chrom1, pos1, chrom2, pos2, zero_based=zero_based)
-        dropped += res["dropped"]
-        part = DeviceCool.from_device_csr(empty, res["indptr"], res["indices"], res["data"], res["nnz"], res["val_dtype"], weight=None,
+        running.add(pairs_csr(dev, geo, chrom1, pos1, chrom2, pos2, zero_based=zero_based))
+    return running.result()
+
+
+class _RunningTable:
+    """The table of the chunks binned so far: what pairs_device and pairs_file_device fold their chunks into."""
+
+    def __init__(self, geo, dev):
+        from .pipeline import DeviceCool
+        none = np.zeros(0, dtype=np.int64)
+        self.table = DeviceCool({"binsize": geo.binsize, "chrom_offset": geo.offsets, "chrom_names": np.asarray(geo.names, dtype=str),
+                                 "bin1_id": none, "bin2_id": none, "count": none, "weight": None, "bin_start": geo.bin_start,
+                                 "bin_end": geo.bin_end}, dev)
+        self.empty = self.table                     # the parent from_device_csr wants: the geometry, no pixels, no weights
+        self.dropped = 0
+
+    def add(self, res):
+        """Merge the table of one chunk (what pairs_csr returns; the caller keeps no reference to its buffers)."""
+        from .pipeline import DeviceCool
+        self.dropped += res["dropped"]
+        part = DeviceCool.from_device_csr(self.empty, res["indptr"], res["indices"], res["data"], res["nnz"], res["val_dtype"], weight=None,
                                           upper=True)
-        del res
-        table = part if table.nnz == 0 else (table if part.nnz == 0 else table.merged(part))
-        del part
-    table.dropped = dropped
-    return table
+        table = self.table
+        self.table = part if table.nnz == 0 else (table if part.nnz == 0 else table.merged(part))
+
+    def result(self):
+        self.table.dropped = self.dropped
+        return self.table
+
+
+# ---- the text of a .pairs file ------------------------------------------------------------------------------------------------------
+class TextReport(NamedTuple):
+    """What the device says about a piece of text: its lines, the index of the first flagged one (-1: none) and why (FLAG_REASONS)."""
+    n_lines: int
+    first_flagged: int
+    reason: int
+
+
+def parse_pairs_text(dev, text, columns, width, names, timings=None):
+    """One piece of the body of a .pairs file parsed on `dev` (cs_pairs_text_count / cs_pairs_text_parse).  text: a bytes-like object,
+    uploaded here, or a device buffer of uint8 that holds exactly the text (never written); columns: the 0-based fields of chr1, pos1,
+    chr2, pos2; width: the most fields a line may have; names: the chromosome names in genome order.  Returns (columns, n, report):
+    the four resident columns as pairs_csr_resident takes them (a list; int32, int64, int32, int64, n entries in line order), the
+    number of lines and a TextReport.  With a flagged line the columns hold nothing of use.  ValueError for columns that are not four
+    distinct fields below width, a name given twice and a text of 2^31 - 1 lines or more.  timings: a dict that receives the seconds
+    of `upload`, `count` and `parse` (each ends in a synchronisation)."""
+    import time
+    encoded = [str(name).encode("utf-8") for name in names]
+    offsets = np.zeros(len(encoded) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in encoded], out=offsets[1:])
+    gathered = b"".join(encoded)
+    fmt = CsPairsTextFormat(*[int(c) for c in columns], int(width), len(encoded), C.cast(C.c_char_p(gathered), C.c_void_p),
+                            offsets.ctypes.data_as(C.c_void_p))
+    t0 = time.perf_counter()
+    with dev.lock:
+        if not isinstance(text, DeviceBuffer):
+            host = np.frombuffer(text, dtype=np.uint8)
+            text = dev.to_device(host) if host.size else dev.empty(0, np.uint8)
+        nbytes = int(text.nbytes)
+        t1 = time.perf_counter()
+        n_lines = C.c_int64(0)
+        report = CsPairsTextReport()
+        try:
+            dev._check(dev.lib.cs_pairs_text_count(dev.ctx, None, text.ptr, nbytes, C.byref(n_lines)))
+            n = int(n_lines.value)
+            t2 = time.perf_counter()
+            if n > MAX_CHUNK_PAIRS:
+                raise ValueError(f"a text of {n} lines: more than 2^31 - 2 are not parsed in one call")
+            cols = [dev.empty(max(n, 1), dtype) for dtype in (np.int32, np.int64, np.int32, np.int64)]
+            dev._check(dev.lib.cs_pairs_text_parse(dev.ctx, None, text.ptr, nbytes, C.byref(fmt), *[c.ptr for c in cols], n, C.byref(report)))
+        except NotImplementedError as exc:          # CS_ERR_UNSUPPORTED: a limit of the kernel, not a missing feature
+            raise ValueError(str(exc)) from None
+        t3 = time.perf_counter()
+    if timings is not None:
+        for key, dt in (("upload", t1 - t0), ("count", t2 - t1), ("parse", t3 - t2)):
+            timings[key] = timings.get(key, 0.0) + dt
+    return cols, n, TextReport(int(report.n_lines), int(report.first_flagged), int(report.reason))
+
+
+class GzipSource:
+    """read(n) over the inflated bytes of a gzip file, member after member (zlib.decompressobj(wbits=31)), never holding more than
+    a block of the file and what one read returns.  EOFError for a file that ends inside a member, zlib.error for one that is none."""
+    BLOCK = 1 << 20
+
+    def __init__(self, handle):
+        self.handle = handle
+        self.inflater = zlib.decompressobj(wbits=31)
+        self.raw = b""                      # bytes of the file not yet given to the inflater
+        self.in_member = False
+
+    def read(self, n):
+        out, got = [], 0
+        while got < n:
+            if self.inflater.eof:
+                self.raw = self.inflater.unused_data.lstrip(b"\0")        # (zero padding between members, as gzip allows)
+                self.inflater = zlib.decompressobj(wbits=31)
+                self.in_member = False
+            if not self.raw:
+                self.raw = self.handle.read(self.BLOCK)
+                if not self.raw:
+                    if not self.in_member:
+                        break
+                    data = self.inflater.decompress(b"", n - got)          # (output the inflater held back at the last limit)
+                    if not data and not self.inflater.eof:
+                        raise EOFError("Compressed file ended before the end-of-stream marker was reached")
+                    out.append(data)
+                    got += len(data)
+                    continue
+                if not self.in_member:
+                    self.raw = self.raw.lstrip(b"\0")
+                    if not self.raw:
+                        continue
+            self.in_member = True
+            data = self.inflater.decompress(self.raw, n - got)
+            self.raw = self.inflater.unconsumed_tail
+            if data:
+                out.append(data)
+                got += len(data)
+        return b"".join(out)
+
+
+def text_pieces(read, piece_bytes, carry=b""):
+    """The text that read(n) -> bytes (b"" at its end) delivers, behind `carry`, as pieces that end at a line end: about piece_bytes
+    are read at a time and cut at their last '\n' (bytes.rfind), and the rest is carried into the next piece, of which that much
+    less is read; a carry without a line end as long as a piece grows by whole reads until it has one or the text ends.  The last
+    piece is whatever is left, with or without a final '\n'.  The pieces, joined, are the text; none is empty.  A piece is bytes-like:
+    where it is the head of one read it is a memoryview of it, not a copy."""
+    piece_bytes = int(piece_bytes)
+    if piece_bytes < 1:
+        raise ValueError(f"piece_bytes must be at least 1, got {piece_bytes}")
+    if carry:                                       # served first, in reads like any other
+        source, pending = read, [carry]
+
+        def read(n):
+            if pending[0]:
+                out, pending[0] = pending[0][:n], pending[0][n:]
+                return out
+            return source(n)
+    held, size = [], 0                              # bytes without a line end, in front of the next block
+    block = read(piece_bytes)
+    while block:
+        cut = block.rfind(b"\n")
+        if cut < 0:
+            held.append(block)
+            size += len(block)
+        else:
+            head = block if cut + 1 == len(block) else memoryview(block)[:cut + 1]
+            yield b"".join(held + [head]) if held else head
+            rest = block[cut + 1:]
+            held, size = ([rest], len(rest)) if rest else ([], 0)
+        block = read(piece_bytes - size if size < piece_bytes else piece_bytes)
+    if held:
+        yield b"".join(held)
+
+
+def _skip_header(read, n_lines, path):
+    """Reads past the first n_lines lines of a file (its header); returns the bytes read beyond them.  DevicePairsRefused for a
+    header line with a carriage return that does not end it: the host reader counts lines in another way then."""
+    from .pipeline import DevicePairsRefused
+    buf, at = b"", 0
+    for k in range(n_lines):
+        while True:
+            end = buf.find(b"\n", at)
+            if end >= 0:
+                break
+            block = read(1 << 16)
+            if not block:
+                return b""                          # (the file ends in its header)
+            buf = buf[at:] + block
+            at = 0
+        if b"\r" in buf[at:end - 1]:
+            raise DevicePairsRefused(f"{path}, line {k + 1}: {FLAG_REASONS[6]}")
+        at = end + 1
+    return buf[at:]
+
+
+def parsed_pieces(pairs_file, piece_bytes, parse, timings=None):
+    """The body of a .pairs file, piece by piece (text_pieces; .gz: inflated on the host as a stream, GzipSource), through
+    parse(piece, columns, width, names) -> (columns, n, TextReport): yields (columns, n) per piece.  pairs_file: the io.PairsFile of
+    the file -- its header pass gives the columns, the width and the number of header lines, which are skipped here.
+    pipeline.DevicePairsRefused (a ValueError) for the first flagged line, named by its 1-based number in the file: the header's
+    lines + the lines of the pieces before + its index + 1.  timings: a dict that receives the seconds spent in `read` and in
+    `cut` (finding the line ends, carrying and joining)."""
+    import time
+    from .pipeline import DevicePairsRefused
+    pf = pairs_file
+    width = max(pf.width, max(pf.columns) + 1)      # (a short first line: the parser flags it, as the host refuses it)
+    names = list(pf.chromsizes)
+    lines_before = pf.header_lines
+    with open(pf.path, "rb") as handle:
+        read = GzipSource(handle).read if pf.path.endswith(".gz") else handle.read
+        if timings is not None:
+            raw_read = read
+
+            def read(n):
+                t0 = time.perf_counter()
+                block = raw_read(n)
+                timings["read"] = timings.get("read", 0.0) + time.perf_counter() - t0
+                return block
+        carry = _skip_header(read, pf.header_lines, pf.path)
+        pieces = text_pieces(read, piece_bytes, carry)
+        while True:
+            t0, read0 = time.perf_counter(), (timings or {}).get("read", 0.0)
+            piece = next(pieces, None)
+            if timings is not None:
+                timings["cut"] = timings.get("cut", 0.0) + time.perf_counter() - t0 - (timings.get("read", 0.0) - read0)
+            if piece is None:
+                break
+            cols, n, report = parse(piece, pf.columns, width, names)
+            if report.first_flagged >= 0:
+                raise DevicePairsRefused(f"{pf.path}, line {lines_before + report.first_flagged + 1}: "
+                                         f"{FLAG_REASONS.get(report.reason, f'reason {report.reason}')}")
+            del piece
+            yield cols, n
+            lines_before += n
+
+
+def pairs_file_device(pairs_file, binsize, zero_based=False, piece_bytes=None, dev=None, timings=None):
+    """DeviceCool.from_pairs_file on its device route: the table of a .pairs file (pairs_file: its io.PairsFile) whose text is parsed
+    on the device.  Every piece of parsed_pieces goes through parse_pairs_text, is binned (pairs_csr_resident) and merged into the
+    running table as pairs_device merges a chunk; the binning is exact, so the table is that of pairs_device over the host reader's
+    chunks, bit for bit, for every piece_bytes (default PIECE_BYTES).  The peak in HBM is a piece's text + its columns (24 bytes per
+    line), and, once the text is released, what pairs_device states for a chunk of that many pairs.  pipeline.DevicePairsRefused
+    for a flagged line; ValueError as pairs_csr for pairs outside the genome.  timings: a dict that receives the seconds of `read`,
+    `cut`, `upload`, `count`, `parse` and `bin` (binning and merge)."""
+    import time
+    dev = dev or get_device()
+    piece_bytes = PIECE_BYTES if piece_bytes is None else int(piece_bytes)
+    if piece_bytes < 1:
+        raise ValueError(f"piece_bytes must be at least 1, got {piece_bytes}")
+    geo = bin_geometry(pairs_file.chromsizes, binsize)
+    running = _RunningTable(geo, dev)
+
+    def parse(piece, columns, width, names):
+        return parse_pairs_text(dev, piece, columns, width, names, timings=timings)
+
+    for cols, n in parsed_pieces(pairs_file, piece_bytes, parse, timings):
+        t0 = time.perf_counter()
+        running.add(pairs_csr_resident(dev, geo, cols, n, zero_based=zero_based))
+        if timings is not None:
+            timings["bin"] = timings.get("bin", 0.0) + time.perf_counter() - t0
+    return running.result()

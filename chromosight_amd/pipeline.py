@@ -15,6 +15,7 @@ import ctypes as C
 import os
 
 import threading
+import zlib
 
 import numpy as np
 import pandas as pd
@@ -490,6 +491,31 @@ class DeviceCool:
         set_weights, or pipeline.open_pairs)."""
         from .cload import pairs_device
         return pairs_device(chunks, chromsizes, binsize, zero_based=zero_based, dev=dev)
+
+    @classmethod
+    def from_pairs_file(cls, path, binsize, chromsizes=None, *, zero_based=False, parse="auto", piece_bytes=None, dev=None):
+        """from_pairs for a 4DN .pairs / .pairs.gz file.  chromsizes: ordered name -> length in bp; None takes the #chromsize: lines
+        of the file.  parse: where the text becomes columns.  "host": io.read_pairs (pandas), chunk by chunk into from_pairs.
+        "device": the header pass stays on the host; the body goes to HBM in pieces of about `piece_bytes` (default
+        cload.PIECE_BYTES; a .gz is inflated on the host as a stream), is parsed there (cs_pairs_text_parse, chromosight_amd/csrc/
+        cs_pairs_text.hip) and binned and merged piece by piece -- the same table, bit for bit, for every piece size.  The device
+        takes a strict subset of what the host reader takes (include/chromosight_hip.h: tab-separated ASCII lines of bounded
+        length, positions of 1 to 18 digits, no empty line); DevicePairsRefused (a ValueError) names the first line it flags.
+        "auto": the device when AUTO_PARSE_ON_DEVICE says so, and the host reader for the whole file -- its table, its `.dropped`
+        and its exceptions -- as soon as the device route raises a ValueError.  CHROMOSIGHT_HIP_HOST_PARSE=1 in the environment
+        forces the host route (ValueError together with parse="device")."""
+        from . import cload, io as cio
+        route = _parse_route(parse)
+        if piece_bytes is not None and (isinstance(piece_bytes, bool) or int(piece_bytes) != piece_bytes or int(piece_bytes) < 1):
+            raise ValueError(f"piece_bytes must be a positive integer, got {piece_bytes!r}")
+        pairs_file = cio.read_pairs(path, chromsizes)
+        if route != "host":
+            try:
+                return cload.pairs_file_device(pairs_file, binsize, zero_based=zero_based, piece_bytes=piece_bytes, dev=dev)
+            except (ValueError, EOFError, zlib.error):          # (DevicePairsRefused is a ValueError)
+                if route == "device":
+                    raise
+        return cls.from_pairs(pairs_file, pairs_file.chromsizes, binsize, zero_based=zero_based, dev=dev)
 
     @classmethod
     def from_cool_file(cls, path, *, balance="weight", dev=None):
@@ -1466,6 +1492,26 @@ def _decode_route(decode):
     return decode if decode != "auto" or AUTO_DECODE_ON_DEVICE else "host"
 
 
+class DevicePairsRefused(ValueError):
+    """A line of the file is outside what the device parses (DeviceCool.from_pairs_file, open_pairs(parse="device"))."""
+
+
+AUTO_PARSE_ON_DEVICE = True         # what open_pairs(parse="auto") does with a .pairs file (tools/time_pairs_parse.py: the device
+                                    # route is faster end to end on both inputs, profiles/pairs_parse_time.json)
+
+
+def _parse_route(parse):
+    """open_pairs' `parse` under the environment and the measured default: "auto" (the device, the host for a file it refuses),
+    "host" or "device"."""
+    if parse not in ("auto", "host", "device"):
+        raise ValueError("parse must be one of: auto, host, device")
+    if os.environ.get("CHROMOSIGHT_HIP_HOST_PARSE", "") not in ("", "0"):
+        if parse == "device":
+            raise ValueError("parse='device' while CHROMOSIGHT_HIP_HOST_PARSE forces the host route")
+        return "host"
+    return parse if parse != "auto" or AUTO_PARSE_ON_DEVICE else "host"
+
+
 def device_decode_refusal(indexes, max_chunk_bytes):
     """Why the pixel columns of a file are not decoded on the device, or None when they are.  indexes: name -> hdf5_lite.ChunkIndex
     of pixels/bin1_id, bin2_id and count (None: not a chunked dataset); max_chunk_bytes: engine.inflate_max_chunk_bytes()."""
@@ -1618,7 +1664,7 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
 
 def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, norm="auto", inter=False, n_mads=5, dev=None,
-               resolution=None):
+               resolution=None, parse="auto", piece_bytes=None):
     """Read pairs (a 4DN .pairs / .pairs.gz path, or an iterable of (chrom1, pos1, chrom2, pos2) chunks of arrays as
     io.read_pairs yields them) binned at `binsize` bp on the device (DeviceCool.from_pairs: what `cooler cload pairs` writes, which
     the reference expects to have been run beforehand) and given weights as open_cool gives them to a file without stored ones:
@@ -1626,19 +1672,25 @@ def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, no
     name -> length in bp; None takes the #chromsize: lines of the file (a path only).  zero_based: the positions are taken as they
     are instead of 1-based.  resolution: None, or a positive multiple of `binsize` to coarsen the binned table to first, as in
     open_cool.  `.dropped` is the number of pairs left out for a chromosome that is not in `chromsizes`.  The binning is exact, so
-    every rank of a parallel run that bins its own copy gets the same table and weights."""
+    every rank of a parallel run that bins its own copy gets the same table and weights.
+    parse, piece_bytes: where the text of a file becomes columns, as in DeviceCool.from_pairs_file ("auto", "host" or "device"; both
+    routes give the same table, bit for bit).  Chunks are parsed already: anything but "auto" with them is a ValueError."""
     if norm not in ("auto", "raw", "force"):
         raise ValueError("norm must be one of: auto, raw, force")
+    if parse not in ("auto", "host", "device"):
+        raise ValueError("parse must be one of: auto, host, device")
     geometry_binsize = int(binsize)
     factor = _resolution_factor(resolution, geometry_binsize)
     chunks = path_or_chunks
     if isinstance(chunks, (str, bytes)) or hasattr(chunks, "__fspath__"):
-        from . import io as cio
-        chunks = cio.read_pairs(chunks, chromsizes)
-        chromsizes = chunks.chromsizes
+        dcool = DeviceCool.from_pairs_file(chunks, geometry_binsize, chromsizes, zero_based=zero_based, parse=parse,
+                                           piece_bytes=piece_bytes, dev=dev)
+    elif parse != "auto":
+        raise ValueError(f"parse={parse!r} takes files: chunks are parsed columns already")
     elif chromsizes is None:
         raise ValueError("open_pairs needs chromsizes for pairs that do not come from a file")
-    dcool = DeviceCool.from_pairs(chunks, chromsizes, geometry_binsize, zero_based=zero_based, dev=dev)
+    else:
+        dcool = DeviceCool.from_pairs(chunks, chromsizes, geometry_binsize, zero_based=zero_based, dev=dev)
     dropped = dcool.dropped
     dcool = _coarsen_and_balance(dcool, factor, True, norm, inter, n_mads)
     dcool.dropped = dropped

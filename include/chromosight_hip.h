@@ -485,6 +485,48 @@ int cs_pairs_count(cs_ctx* ctx, void* stream, const int32_t* d_chrom1, const int
 int cs_pairs_fill(cs_ctx* ctx, void* stream, const int64_t* d_keys, int64_t n_pairs, cs_csr* out);
 int32_t cs_pairs_block_pairs(void);
 
+/* ---- the body text of a 4DN .pairs file parsed in HBM into the four columns cs_pairs_count takes (cs_pairs_text.hip) ----------------
+ * d_text: nbytes (< 2^40; more: CS_ERR_UNSUPPORTED) bytes of body text on the device, starting at a multiple of 16 bytes (anything
+ * else: CS_ERR_INVALID); no byte at or beyond nbytes is read, so no padding is asked of the caller.  Lines end at '\n'; a last line
+ * without '\n' is a line, a trailing '\n' opens none.  cs_pairs_text_format: the 0-based fields of chr1, pos1, chr2 and pos2 (distinct,
+ * each below width), width = the most fields a line may have, and the n_names (< 2^30) chromosome names in genome order as host
+ * arrays: their bytes one after the other and n_names + 1 offsets from 0 (below 2^31); a name given twice: CS_ERR_INVALID.
+ * A line is accepted when: one '\r' directly before its '\n' is dropped and no other '\r' occurs; its fields, split at '\t', number
+ * more than its largest column and at most width; both positions are 1 to 18 ASCII digits and nothing else (leading zeros count as
+ * digits); both names are non-empty; it holds no NUL byte and no byte >= 0x80; and at most cs_pairs_text_max_line_bytes() bytes stand
+ * in front of its terminator.  A name is compared bytewise with the format's names: its id, or -1 when it is none of them.  Every other
+ * line is flagged, with the first defect met from the left: 1 an empty line, 2 too few fields, 3 too many fields, 4 an empty name or
+ * position, 5 a position that is not 1 to 18 digits, 6 a '\r' not directly before '\n', 7 a NUL byte, 8 a byte >= 0x80, 9 a line
+ * over the cap.
+ * cs_pairs_text_count reports the number of lines.  An empty text: 0 lines, no launch.
+ * cs_pairs_text_parse writes the columns in line order, exactly n_lines (< 2^31 - 1; more: CS_ERR_UNSUPPORTED) entries each -- n_lines
+ *   must be what cs_pairs_text_count reports for the text (CS_ERR_INVALID otherwise, nothing written) -- and the report: the number of
+ *   lines, the smallest index of a flagged line (-1: none) and that line's reason.  The report is the same for every launch shape and
+ *   device (an integer minimum).  The columns of a call with a flagged line hold nothing of use.
+ * cs_pairs_text_tile_bytes: the bytes of text one workgroup covers; cs_pairs_text_max_line_bytes: the cap (tests and documents).
+ * cs_pairs_text_name_slot: the slot of the name table (which has one slot for twice the names at the least, probed linearly) that a
+ *   name of `len` bytes hashes to among n_names names; -1 for a null name or a bad count (tests).
+ * Both calls are synchronous; the text is never written. */
+typedef struct {
+    int32_t col_chrom1, col_pos1, col_chrom2, col_pos2;
+    int32_t width;
+    int32_t n_names;
+    const uint8_t* h_name_bytes;
+    const int64_t* h_name_offsets;
+} cs_pairs_text_format;
+typedef struct {
+    int64_t n_lines;
+    int64_t first_flagged;
+    int32_t reason;
+    int32_t reserved;
+} cs_pairs_text_report;
+int cs_pairs_text_count(cs_ctx* ctx, void* stream, const void* d_text, int64_t nbytes, int64_t* h_n_lines);
+int cs_pairs_text_parse(cs_ctx* ctx, void* stream, const void* d_text, int64_t nbytes, const cs_pairs_text_format* fmt, int32_t* d_chrom1,
+                        int64_t* d_pos1, int32_t* d_chrom2, int64_t* d_pos2, int64_t n_lines, cs_pairs_text_report* h_report);
+int32_t cs_pairs_text_tile_bytes(void);
+int32_t cs_pairs_text_max_line_bytes(void);
+int32_t cs_pairs_text_name_slot(const uint8_t* name, int64_t len, int64_t n_names);
+
 /* ---- the pixel columns of a .cool decoded from file bytes in HBM: what the HDF5 library does for cooler on the host (chunks of a
  * 1-D dataset through the filters shuffle, gzip and Fletcher-32), and what pipeline.DeviceCool's constructor makes of the three
  * columns ----
