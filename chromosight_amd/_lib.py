@@ -435,6 +435,17 @@ def np_dtype_code(dtype):
     raise TypeError(f"unsupported dtype {dtype}")
 
 
+def np_dtype_of(code):
+    """The inverse of np_dtype_code: the numpy type of the values a kernel reports as CS_F32 / CS_F64."""
+    return {CS_F32: np.float32, CS_F64: np.float64}[int(code)]
+
+
+def plain_csr(n, nnz, indptr, indices, data, dtype):
+    """The plain cs_csr (no view, no weights) of n x n bins over device buffers; dtype: of the values in `data` (an output table's
+    buffer may be wider than what the kernel is asked to start from)."""
+    return CsCsr(n, n, nnz, indptr.ptr, indices.ptr, data.ptr, np_dtype_code(dtype), 0, None, None, None)
+
+
 class DeviceBuffer:
     """A typed HBM allocation owned by a Device (freed on garbage collection)."""
 

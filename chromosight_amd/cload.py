@@ -33,7 +33,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import CS_F32, CsCsr, CsPairsTextFormat, CsPairsTextReport, DeviceBuffer, get_device, load_library, np_dtype_code
+from ._lib import CsPairsTextFormat, CsPairsTextReport, DeviceBuffer, get_device, load_library, np_dtype_of, plain_csr
 
 MAX_CHUNK_PAIRS = 2 ** 31 - 2
 PIECE_BYTES = 1 << 27           # the text of a file that goes to the device at a time (pairs_file_device)
@@ -145,10 +145,10 @@ def pairs_csr_resident(dev, geometry, columns, n, zero_based=False):
             if isinstance(columns, list):
                 columns.clear()
             nnz = int(out_nnz.value)
-            val_dtype = np.float32 if out_dtype.value == CS_F32 else np.float64
+            val_dtype = np_dtype_of(out_dtype.value)
             indices = dev.empty(max(nnz, 1), np.int32)
             data = dev.empty(max(nnz, 1), val_dtype)
-            out = CsCsr(n_bins, n_bins, nnz, indptr.ptr, indices.ptr, data.ptr, np_dtype_code(val_dtype), 0, None, None, None)
+            out = plain_csr(n_bins, nnz, indptr, indices, data, val_dtype)
             dev._check(dev.lib.cs_pairs_fill(dev.ctx, None, keys.ptr, n, C.byref(out)))
         except NotImplementedError as exc:          # CS_ERR_UNSUPPORTED: a limit of the kernel, not a missing feature
             raise ValueError(str(exc)) from None
@@ -182,26 +182,32 @@ class _RunningTable:
     """The table of the chunks binned so far: what pairs_device and pairs_file_device fold their chunks into."""
 
     def __init__(self, geo, dev):
+        self.geo, self.dev, self.dropped = geo, dev, 0
+        # the CSR so far, as merge.merge_csr returns it; before the first chunk the table without pixels, as the constructor uploads it
+        self.table = {"indptr": dev.zeros(int(geo.offsets[-1]) + 1, np.int64), "indices": dev.empty(0, np.int32),
+                      "data": dev.empty(0, np.float32), "nnz": 0, "val_dtype": np.float32}
+
+    def _over(self, table, dropped=None):
+        """The DeviceCool of a table of pairs over the geometry: counts that are exact exactly when they are float32 (they are
+        non-negative integers), every pixel on or above the diagonal, no weights."""
         from .pipeline import DeviceCool
-        none = np.zeros(0, dtype=np.int64)
-        self.table = DeviceCool({"binsize": geo.binsize, "chrom_offset": geo.offsets, "chrom_names": np.asarray(geo.names, dtype=str),
-                                 "bin1_id": none, "bin2_id": none, "count": none, "weight": None, "bin_start": geo.bin_start,
-                                 "bin_end": geo.bin_end}, dev)
-        self.empty = self.table                     # the parent from_device_csr wants: the geometry, no pixels, no weights
-        self.dropped = 0
+        geo = self.geo
+        return DeviceCool._from_table(self.dev, names=geo.names, offsets=geo.offsets, binsize=geo.binsize, bin_start=geo.bin_start,
+                                      bin_end=geo.bin_end, counts_exact=table["val_dtype"] is np.float32, upper=True, weight=None,
+                                      dropped=dropped, **table)
 
     def add(self, res):
         """Merge the table of one chunk (what pairs_csr returns; the caller keeps no reference to its buffers)."""
-        from .pipeline import DeviceCool
+        from .merge import merge_csr
         self.dropped += res["dropped"]
-        part = DeviceCool.from_device_csr(self.empty, res["indptr"], res["indices"], res["data"], res["nnz"], res["val_dtype"], weight=None,
-                                          upper=True)
-        table = self.table
-        self.table = part if table.nnz == 0 else (table if part.nnz == 0 else table.merged(part))
+        part = {key: res[key] for key in ("indptr", "indices", "data", "nnz", "val_dtype")}
+        if self.table["nnz"] == 0:
+            self.table = part
+        elif part["nnz"]:
+            self.table = merge_csr([self._over(self.table), self._over(part)])
 
     def result(self):
-        self.table.dropped = self.dropped
-        return self.table
+        return self._over(self.table, self.dropped)
 
 
 # ---- the text of a .pairs file ------------------------------------------------------------------------------------------------------

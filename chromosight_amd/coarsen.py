@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CS_F32, CsCsr, np_dtype_code
+from ._lib import np_dtype_of, plain_csr
 
 
 def check_factor(factor):
@@ -70,7 +70,7 @@ def coarsen_csr(dcool, factor):
     indptr = dev.empty(n_coarse + 1, np.int64)
     indices = dev.empty(max(nnz, 1), np.int32)
     data = dev.empty(max(nnz, 1), np.float64)
-    out = CsCsr(n_coarse, n_coarse, 0, indptr.ptr, indices.ptr, data.ptr, np_dtype_code(np.float32), 0, None, None, None)
+    out = plain_csr(n_coarse, 0, indptr, indices, data, np.float32)
     out_nnz = C.c_int64(0)
     genome = dcool.csr()
     with dev.lock:
@@ -79,8 +79,7 @@ def coarsen_csr(dcool, factor):
     if out.n_rows != n_coarse:
         raise RuntimeError(f"cs_coarsen made {out.n_rows} coarse bins, the host geometry {n_coarse}")
     return {"indptr": indptr, "indices": indices, "data": data, "nnz": int(out_nnz.value),
-            "val_dtype": np.float32 if out.dtype == CS_F32 else np.float64, "offsets": offsets, "bin_start": start, "bin_end": end,
-            "binsize": binsize}
+            "val_dtype": np_dtype_of(out.dtype), "offsets": offsets, "bin_start": start, "bin_end": end, "binsize": binsize}
 
 
 def coarsen_device(dcool, factor):

@@ -596,7 +596,7 @@ def run_table_from_columns(dev, bin1, bin2, count, nnz, n_bins, stream=None):
     rep = _lib.CsTableReport()
     dev._check(dev.lib.cs_table_from_columns_count(dev.ctx, stream, bin1.ptr, bin2.ptr, bin1.dtype.itemsize, count.ptr, count.dtype.itemsize, nnz,
                                                    n_bins, indptr.ptr, indices.ptr, C.byref(rep)))
-    val_dtype = np.float32 if rep.dtype == CS_F32 else np.float64
+    val_dtype = _lib.np_dtype_of(rep.dtype)
     out = {"indptr": indptr, "indices": indices, "data": None, "nnz": nnz, "val_dtype": val_dtype, "ids_ok": bool(rep.ids_ok),
            "sorted": bool(rep.sorted), "upper": bool(rep.upper), "count_min": int(rep.count_min), "count_max": int(rep.count_max)}
     if out["ids_ok"] and out["sorted"]:

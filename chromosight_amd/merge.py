@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CS_F32, CsCsr, load_library, np_dtype_code
+from ._lib import CsCsr, load_library, np_dtype_of, plain_csr
 
 MAX_SOURCES = 64
 
@@ -76,10 +76,10 @@ def merge_csr(dcools):
         try:
             dev._check(dev.lib.cs_merge_count(dev.ctx, None, tables, len(csrs), indptr.ptr, C.byref(out_nnz), C.byref(out_dtype)))
             nnz = int(out_nnz.value)
-            val_dtype = np.float32 if out_dtype.value == CS_F32 else np.float64
+            val_dtype = np_dtype_of(out_dtype.value)
             indices = dev.empty(max(nnz, 1), np.int32)
             data = dev.empty(max(nnz, 1), val_dtype)
-            out = CsCsr(n, n, nnz, indptr.ptr, indices.ptr, data.ptr, np_dtype_code(val_dtype), 0, None, None, None)
+            out = plain_csr(n, nnz, indptr, indices, data, val_dtype)
             dev._check(dev.lib.cs_merge_fill(dev.ctx, None, tables, len(csrs), C.byref(out)))
         except NotImplementedError as exc:          # CS_ERR_UNSUPPORTED: a limit of the kernel, not a missing feature
             raise ValueError(str(exc)) from None

@@ -24,7 +24,7 @@ import scipy.sparse as sp
 from . import engine
 from ._lib import (COUNTS_HEADER_BYTES, CS_F32, CS_F64, FOCUS_DTYPE, LAYOUT_BAND, LAYOUT_BAND_COUNTS, LAYOUT_BAND_COUNTS_VIEW, LAYOUT_BAND_LAZY,
                    LAYOUT_BAND_PADDED, LAYOUT_DENSE, LAZY_BAND_BYTES, MASK_BINS, STAGE_SMOOTH, CsCsr, CsMatrix, CsStageBlock,
-                   get_device, np_dtype_code)
+                   get_device, np_dtype_code, plain_csr)
 from .utils import detection as cid
 from .utils import preprocessing as preproc
 from .utils.stats import fdr_correction
@@ -405,45 +405,69 @@ class DeviceCool:
     contacts_map.py:531), the slicing of the block, diag_trim, the distance law, detrend and the
     band tiler all read the same arrays (cs_csr views, include/chromosight_hip.h)."""
 
-    _host_dtypes = (np.int64, np.int64, np.int64)      # of bin1_id, bin2_id, count in a `.host` that is downloaded
-
     def __init__(self, cool, dev=None):
-        if isinstance(cool, (str, bytes)) or hasattr(cool, "__fspath__"):
+        if _is_path(cool):
             from . import io as cio
             cool = cio.load_cool(cool)                     # a .cool path: decoded here (chromosight_amd/io.py)
-        self.dev = dev = dev or get_device()
+        dev = dev or get_device()
         off = np.asarray(cool["chrom_offset"], dtype=np.int64)
-        self.offsets = off
-        self.n_bins = n_bins = int(off[-1])
-        self.names = [str(n) for n in cool["chrom_names"]]
-        self.binsize = int(cool["binsize"])
-        self.bin_start, self.bin_end = cool.get("bin_start"), cool.get("bin_end")
         b1 = np.asarray(cool["bin1_id"])
         b2 = np.asarray(cool["bin2_id"])
         cnt = np.asarray(cool["count"])
         if b1.size and not (np.all(b1[1:] >= b1[:-1]) and np.all((b1[1:] > b1[:-1]) | (b2[1:] > b2[:-1]))):
             order = np.lexsort((b2, b1))                      # unsorted / duplicated pixel table
             b1, b2, cnt = b1[order], b2[order], cnt[order]
-        # no "weight" (or None): a table without balancing weights -- nothing is staged from it until set_weights()
-        # (pipeline.open_cool balances it on the device: chromosight_amd/balance.py)
-        weight = cool.get("weight") if hasattr(cool, "get") else cool["weight"]
-        indptr = np.searchsorted(b1, np.arange(n_bins + 1)).astype(np.int64)
+        indptr = np.searchsorted(b1, np.arange(int(off[-1]) + 1)).astype(np.int64)
         # integer counts below 2^24 are exact in float32 (half the bytes of every pass)
         small = cnt.size == 0 or (np.issubdtype(cnt.dtype, np.integer) and cnt.max() < (1 << 24)) or \
             (cnt.max() < (1 << 24) and np.all(cnt == np.rint(cnt)))
-        self.val_dtype = np.float32 if small else np.float64
-        # ... and, when none is negative, can be staged as a band of raw counts that its readers detrend (CS_LAYOUT_BAND_COUNTS)
-        # (and no weight: the readers' NaN -> 0 is a max with 0)
-        self._counts_exact = bool(small and (cnt.size == 0 or cnt.min() >= 0))
-        self.nnz = int(b1.size)
-        self.indptr = dev.to_device(indptr, np.int64)
-        self.indices = dev.to_device(b2, np.int32)
-        self.data = dev.to_device(cnt, self.val_dtype)
-        self._host = {"binsize": self.binsize, "chrom_offset": off, "chrom_names": np.asarray(self.names), "bin1_id": b1,
-                      "bin2_id": b2, "count": cnt, "weight": None, "bin_start": self.bin_start, "bin_end": self.bin_end}
-        # what cs_stage_blocks needs: every stored pixel on or above the diagonal (a .cool's symmetric-upper storage)
-        self.upper = bool(b1.size == 0 or np.all(b2 >= b1))
-        self._init_resident(weight)
+        val_dtype = np.float32 if small else np.float64
+        self._set_table(
+            dev, names=cool["chrom_names"], offsets=off, binsize=cool["binsize"], bin_start=cool.get("bin_start"), bin_end=cool.get("bin_end"),
+            indptr=dev.to_device(indptr, np.int64), indices=dev.to_device(b2, np.int32), data=dev.to_device(cnt, val_dtype),
+            nnz=b1.size, val_dtype=val_dtype,
+            # ... and, when none is negative, can be staged as a band of raw counts that its readers detrend (CS_LAYOUT_BAND_COUNTS)
+            # (and no weight: the readers' NaN -> 0 is a max with 0)
+            counts_exact=small and (cnt.size == 0 or cnt.min() >= 0),
+            # what cs_stage_blocks needs: every stored pixel on or above the diagonal (a .cool's symmetric-upper storage)
+            upper=b1.size == 0 or np.all(b2 >= b1),
+            # no "weight" (or None): a table without balancing weights -- nothing is staged from it until set_weights()
+            # (pipeline.open_cool balances it on the device: chromosight_amd/balance.py)
+            weight=cool.get("weight"), host=(b1, b2, cnt))
+
+    def _set_table(self, dev, *, names, offsets, binsize, bin_start, bin_end, indptr, indices, data, nnz, val_dtype, counts_exact, upper,
+                   weight, host=None, host_dtypes=(np.int64, np.int64, np.int64), dropped=None):
+        """What a resident pixel table consists of: the ONE place that fills in a DeviceCool (the constructor ends here, tables
+        built on the device come through _from_table; nothing else assigns these fields).  indptr, indices, data: the device buffers
+        of the CSR, the first nnz entries used.  counts_exact: every count is a non-negative integer below 2^24.  upper: every pixel
+        lies on or above the diagonal; None has it checked on the pixels (a download).  weight: None for a table without.  host:
+        the (bin1_id, bin2_id, count) columns where the caller holds them; None has `.host` download them when first read, in
+        host_dtypes.  dropped: the pairs left out of a table binned from pairs, None for any other table."""
+        self.dev, self.names, self.offsets, self.n_bins = dev, [str(n) for n in names], offsets, int(offsets[-1])
+        self.binsize, self.bin_start, self.bin_end = int(binsize), bin_start, bin_end
+        self.indptr, self.indices, self.data, self.nnz = indptr, indices, data, int(nnz)
+        self.val_dtype, self._counts_exact, self.dropped = np.dtype(val_dtype).type, bool(counts_exact), dropped
+        self._host_dtypes, self._host_weight = host_dtypes, None
+        self._host = None if host is None else self._host_of(*host)
+        self.upper = bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]) if upper is None else upper)
+        self._retired = []
+        self.weight = self.miss = self.det = self.miss_host = None
+        self.counts_ok = False
+        if weight is not None:
+            self.set_weights(weight)
+        self._band = _Scratch(self.dev)
+        self._ext = _Scratch(self.dev)
+        self._strips = _StripPool(self.dev)         # the row strips of trans blocks (allocates when the first one is staged)
+        self._stage_lock = threading.RLock()
+        self._free = _FreeList()        # HBM of released resident blocks, reused by the next staging
+        self._workers = None
+
+    @classmethod
+    def _from_table(cls, dev, **table):
+        """A DeviceCool over a table that is resident already: _set_table's arguments."""
+        self = cls.__new__(cls)
+        self._set_table(dev, **table)
+        return self
 
     @classmethod
     def from_device_csr(cls, parent, indptr, indices, data, nnz, val_dtype, *, offsets=_PARENT, binsize=_PARENT, bin_start=_PARENT,
@@ -456,29 +480,17 @@ class DeviceCool:
         coarsen.coarsen_csr); weight=None makes a table without weights.  The chromosomes and their names stay the parent's, and a
         table whose pixels are the parent's regrouped by a monotone map of the bins is upper-triangle when the parent is.
         upper: whether every pixel lies on or above the diagonal, for a caller that knows (merge.merge_device: all sources do)."""
-        self = cls.__new__(cls)
-        self.dev = parent.dev
-        self.offsets = parent.offsets if offsets is _PARENT else np.asarray(offsets, dtype=np.int64)
-        if self.offsets.shape != parent.offsets.shape:
-            raise ValueError(f"{self.offsets.size} chromosome offsets for the parent's {len(parent.names)} chromosomes")
-        self.n_bins = int(self.offsets[-1])
-        self.names = list(parent.names)
-        self.binsize = parent.binsize if binsize is _PARENT else int(binsize)
-        self.bin_start = parent.bin_start if bin_start is _PARENT else bin_start
-        self.bin_end = parent.bin_end if bin_end is _PARENT else bin_end
-        self.val_dtype = np.dtype(val_dtype).type
-        self._counts_exact = self.val_dtype is np.float32
-        self.nnz = int(nnz)
-        self.indptr, self.indices, self.data = indptr, indices, data
-        weight = parent.host_weight if weight is _PARENT else weight
-        self._host, self._host_weight = None, weight
-        # a subset of an upper-triangle table is one; anything else is checked on the pixels
-        if upper is not _PARENT:
-            self.upper = bool(upper)
-        else:
-            self.upper = True if parent.upper else bool(np.all(self.host["bin2_id"] >= self.host["bin1_id"]))
-        self._init_resident(weight)
-        return self
+        offsets = parent.offsets if offsets is _PARENT else np.asarray(offsets, dtype=np.int64)
+        if offsets.shape != parent.offsets.shape:
+            raise ValueError(f"{offsets.size} chromosome offsets for the parent's {len(parent.names)} chromosomes")
+        if upper is _PARENT:                # a subset of an upper-triangle table is one; anything else is checked on the pixels
+            upper = True if parent.upper else None
+        return cls._from_table(
+            parent.dev, names=parent.names, offsets=offsets, binsize=parent.binsize if binsize is _PARENT else binsize,
+            bin_start=parent.bin_start if bin_start is _PARENT else bin_start, bin_end=parent.bin_end if bin_end is _PARENT else bin_end,
+            indptr=indptr, indices=indices, data=data, nnz=nnz, val_dtype=val_dtype,
+            # (the counts are non-negative integers, so they are exact exactly when they fit float32)
+            counts_exact=np.dtype(val_dtype) == np.float32, upper=upper, weight=parent.host_weight if weight is _PARENT else weight)
 
     @classmethod
     def from_pairs(cls, chunks, chromsizes, binsize, zero_based=False, dev=None):
@@ -530,21 +542,6 @@ class DeviceCool:
         bins, or a table that is not strictly sorted by (bin1, bin2).  engine.CorruptChunks for chunks that do not decode."""
         return _device_cool_from_file(path, balance, dev, lambda cool: cool["weight"])
 
-    def _init_resident(self, weight):
-        self._host_weight = None
-        self._retired = []
-        self.weight = self.miss = self.det = self.miss_host = None
-        self.counts_ok = False
-        self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes
-        if weight is not None:
-            self.set_weights(weight)
-        self._band = _Scratch(self.dev)
-        self._ext = _Scratch(self.dev)
-        self._strips = _StripPool(self.dev)         # the row strips of trans blocks (allocates when the first one is staged)
-        self._stage_lock = threading.RLock()
-        self._free = _FreeList()        # HBM of released resident blocks, reused by the next staging
-        self._workers = None
-
     def set_weights(self, weight):
         """Take new balancing weights (n_bins values, NaN = bin without a weight): uploads `weight` and the missing /
         detectable flags, refreshes counts_ok and the host copy.  The pixel table stays as it is.  The buffers of the
@@ -564,7 +561,6 @@ class DeviceCool:
         self._host_weight = weight
         if self._host is not None:
             self._host["weight"] = weight
-        self.upload_bytes = self.indptr.nbytes + self.indices.nbytes + self.data.nbytes + self.weight.nbytes
 
     @property
     def host(self):
@@ -577,10 +573,18 @@ class DeviceCool:
             b1 = np.repeat(np.arange(self.n_bins, dtype=t1), np.diff(indptr))
             b2 = self.indices.download()[:n].astype(t2)
             cnt = self.data.download().view(self.val_dtype)[:n].astype(tc)
-            self._host = {"binsize": self.binsize, "chrom_offset": self.offsets, "chrom_names": np.asarray(self.names), "bin1_id": b1,
-                          "bin2_id": b2, "count": cnt, "weight": self._host_weight, "bin_start": self.bin_start,
-                          "bin_end": self.bin_end}
+            self._host = self._host_of(b1, b2, cnt)
         return self._host
+
+    def _host_of(self, b1, b2, cnt):
+        return {"binsize": self.binsize, "chrom_offset": self.offsets, "chrom_names": np.asarray(self.names), "bin1_id": b1, "bin2_id": b2,
+                "count": cnt, "weight": self._host_weight, "bin_start": self.bin_start, "bin_end": self.bin_end}
+
+    @property
+    def upload_bytes(self):
+        """The bytes an upload of the table and its weights moves (a buffer filled on the device may have room for more pixels)."""
+        pixels = self.nnz * (self.indices.dtype.itemsize + np.dtype(self.val_dtype).itemsize)
+        return self.indptr.nbytes + pixels + (0 if self.weight is None else self.weight.nbytes)
 
     @property
     def host_weight(self):
@@ -598,8 +602,7 @@ class DeviceCool:
 
     def csr(self):
         """The whole-genome pixel table as a plain cs_csr (no weights)."""
-        return CsCsr(self.n_bins, self.n_bins, self.nnz, self.indptr.ptr, self.indices.ptr, self.data.ptr,
-                     np_dtype_code(self.val_dtype), 0, None, None, None)
+        return plain_csr(self.n_bins, self.nnz, self.indptr, self.indices, self.data, self.val_dtype)
 
     def _resident(self, nbytes, dev=None):
         buf = self._free.take(nbytes)
@@ -746,8 +749,7 @@ class DeviceCool:
                 blk.genome = self                               # (the descriptor points into the pixel table)
                 blk.restage = (lambda ci=ci: self._restage_synced(ci, max_dist, largest_kernel, band_dtype=band_dtype, smooth=smooth))
             blocks.append(blk)
-        genome = CsCsr(self.n_bins, self.n_bins, max(self.nnz, 1), self.indptr.ptr, self.indices.ptr, self.data.ptr,
-                       np_dtype_code(self.val_dtype), 0, None, self.weight.ptr, self.weight.ptr)
+        genome = self._view(0, self.n_bins, 0, self.n_bins)
         # asynchronous on `stream`: whoever reads the blocks on another stream or context synchronises first (the callers
         # that hand blocks to worker threads do; the law scratch is rewritten in stream order)
         with dev.lock:
@@ -1473,6 +1475,11 @@ def _is_path(source):
     return isinstance(source, (str, bytes)) or hasattr(source, "__fspath__")
 
 
+def _check_norm(norm):
+    if norm not in ("auto", "raw", "force"):
+        raise ValueError("norm must be one of: auto, raw, force")
+
+
 class DeviceDecodeRefused(ValueError):
     """The file does not qualify for the device decode (DeviceCool.from_cool_file, open_cool(decode="device"))."""
 
@@ -1481,15 +1488,21 @@ AUTO_DECODE_ON_DEVICE = True        # what open_cool(decode="auto") does with a 
 _PIXEL_COLUMNS = ("bin1_id", "bin2_id", "count")
 
 
-def _decode_route(decode):
-    """open_cool's `decode` under the environment: "auto", "host" or "device"."""
-    if decode not in ("auto", "host", "device"):
-        raise ValueError("decode must be one of: auto, host, device")
-    if os.environ.get("CHROMOSIGHT_HIP_HOST_DECODE", "") not in ("", "0"):
-        if decode == "device":
-            raise ValueError("decode='device' while CHROMOSIGHT_HIP_HOST_DECODE forces the host route")
+def _route(name, value, env, auto_on_device):
+    """Where a loader does its work: the argument `name` = `value` under the environment variable `env` and the measured default
+    for "auto" -- "auto" (the device, the host for a file it refuses), "host" or "device"."""
+    if value not in ("auto", "host", "device"):
+        raise ValueError(f"{name} must be one of: auto, host, device")
+    if os.environ.get(env, "") not in ("", "0"):
+        if value == "device":
+            raise ValueError(f"{name}='device' while {env} forces the host route")
         return "host"
-    return decode if decode != "auto" or AUTO_DECODE_ON_DEVICE else "host"
+    return value if value != "auto" or auto_on_device else "host"
+
+
+def _decode_route(decode):
+    """open_cool's `decode`: _route."""
+    return _route("decode", decode, "CHROMOSIGHT_HIP_HOST_DECODE", AUTO_DECODE_ON_DEVICE)
 
 
 class DevicePairsRefused(ValueError):
@@ -1501,15 +1514,8 @@ AUTO_PARSE_ON_DEVICE = True         # what open_pairs(parse="auto") does with a 
 
 
 def _parse_route(parse):
-    """open_pairs' `parse` under the environment and the measured default: "auto" (the device, the host for a file it refuses),
-    "host" or "device"."""
-    if parse not in ("auto", "host", "device"):
-        raise ValueError("parse must be one of: auto, host, device")
-    if os.environ.get("CHROMOSIGHT_HIP_HOST_PARSE", "") not in ("", "0"):
-        if parse == "device":
-            raise ValueError("parse='device' while CHROMOSIGHT_HIP_HOST_PARSE forces the host route")
-        return "host"
-    return parse if parse != "auto" or AUTO_PARSE_ON_DEVICE else "host"
+    """open_pairs' `parse`: _route."""
+    return _route("parse", parse, "CHROMOSIGHT_HIP_HOST_PARSE", AUTO_PARSE_ON_DEVICE)
 
 
 def device_decode_refusal(indexes, max_chunk_bytes):
@@ -1570,23 +1576,13 @@ def _device_cool_from_file(uri, balance, dev, pick_weight):
     if not res["sorted"]:
         raise DeviceDecodeRefused(f"{uri}: the pixel table is not strictly sorted by (bin1, bin2)")
     del columns
-    self = DeviceCool.__new__(DeviceCool)
-    self.dev = dev
-    self.offsets, self.n_bins = off, n_bins
-    self.names = [str(n) for n in cool["chrom_names"]]
-    self.binsize = int(cool["binsize"])
-    self.bin_start, self.bin_end = cool.get("bin_start"), cool.get("bin_end")
-    self.val_dtype = res["val_dtype"]
-    self._counts_exact = bool(self.val_dtype is np.float32 and (nnz == 0 or res["count_min"] >= 0))
-    self.nnz = nnz
-    self.indptr, self.indices, self.data = res["indptr"], res["indices"], res["data"]
-    self._host = None
     # (io._load narrows the ids of a table that has pixels when all are below 2^31; here every id is below n_bins)
     ids = np.int32 if nnz and n_bins <= 2 ** 31 else indexes["bin1_id"].dtype.type
-    self._host_dtypes = (ids, ids, indexes["count"].dtype.type)
-    self.upper = bool(res["upper"])
-    self._init_resident(pick_weight(cool))
-    return self
+    return DeviceCool._from_table(
+        dev, names=cool["chrom_names"], offsets=off, binsize=cool["binsize"], bin_start=cool.get("bin_start"),
+        bin_end=cool.get("bin_end"), indptr=res["indptr"], indices=res["indices"], data=res["data"], nnz=nnz, val_dtype=res["val_dtype"],
+        counts_exact=res["val_dtype"] is np.float32 and (nnz == 0 or res["count_min"] >= 0), upper=res["upper"],
+        weight=pick_weight(cool), host_dtypes=(ids, ids, indexes["count"].dtype.type))
 
 
 def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weight", dev=None, resolution=None, decode="auto"):
@@ -1622,8 +1618,7 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
     as before, when it does not.  "host": always on the host; CHROMOSIGHT_HIP_HOST_DECODE=1 in the environment does the same.
     "device": on the device, DeviceDecodeRefused (a ValueError) for a file that does not qualify and ValueError for a dictionary,
     which is decoded already.  Both routes give the same table, bit for bit."""
-    if norm not in ("auto", "raw", "force"):
-        raise ValueError("norm must be one of: auto, raw, force")
+    _check_norm(norm)
     route = _decode_route(decode)
     sources = list(uri_or_cool) if isinstance(uri_or_cool, (list, tuple)) else [uri_or_cool]
     if not sources:
@@ -1675,14 +1670,11 @@ def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, no
     every rank of a parallel run that bins its own copy gets the same table and weights.
     parse, piece_bytes: where the text of a file becomes columns, as in DeviceCool.from_pairs_file ("auto", "host" or "device"; both
     routes give the same table, bit for bit).  Chunks are parsed already: anything but "auto" with them is a ValueError."""
-    if norm not in ("auto", "raw", "force"):
-        raise ValueError("norm must be one of: auto, raw, force")
-    if parse not in ("auto", "host", "device"):
-        raise ValueError("parse must be one of: auto, host, device")
+    _check_norm(norm)
     geometry_binsize = int(binsize)
     factor = _resolution_factor(resolution, geometry_binsize)
     chunks = path_or_chunks
-    if isinstance(chunks, (str, bytes)) or hasattr(chunks, "__fspath__"):
+    if _is_path(chunks):                # (from_pairs_file checks `parse`)
         dcool = DeviceCool.from_pairs_file(chunks, geometry_binsize, chromsizes, zero_based=zero_based, parse=parse,
                                            piece_bytes=piece_bytes, dev=dev)
     elif parse != "auto":

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import CS_F32, CsCsr, CsSubsampleBlock, CsSubsampleParams, np_dtype_code
+from ._lib import CsSubsampleBlock, CsSubsampleParams, np_dtype_of, plain_csr
 
 BLOCK_DTYPE = np.dtype([("chrom1", np.int32), ("chrom2", np.int32), ("total", np.int64), ("keep", np.int64)])
 
@@ -44,7 +44,7 @@ def subsample_csr(dcool, sample, seed=0, inter=False, drawn=False):
     indices = dev.empty(max(nnz, 1), np.int32)
     data = dev.empty(max(nnz, 1), np.float64)
     d_drawn = dev.empty(max(nnz, 1), np.int64) if drawn else None
-    out = CsCsr(dcool.n_bins, dcool.n_bins, 0, indptr.ptr, indices.ptr, data.ptr, np_dtype_code(np.float32), 0, None, None, None)
+    out = plain_csr(dcool.n_bins, 0, indptr, indices, data, np.float32)
     params = CsSubsampleParams(sample, seed, int(bool(inter)), 0)
     blocks = (CsSubsampleBlock * max(n_blocks, 1))()
     out_nnz = C.c_int64(0)
@@ -54,8 +54,8 @@ def subsample_csr(dcool, sample, seed=0, inter=False, drawn=False):
                                         C.byref(params), C.byref(out), C.byref(out_nnz), blocks,
                                         d_drawn.ptr if d_drawn is not None else None))
     table = np.frombuffer(bytes(blocks), dtype=BLOCK_DTYPE, count=n_blocks).copy() if n_blocks else np.zeros(0, BLOCK_DTYPE)
-    res = {"indptr": indptr, "indices": indices, "data": data, "nnz": int(out_nnz.value),
-           "val_dtype": np.float32 if out.dtype == CS_F32 else np.float64, "blocks": table, "drawn": None}
+    res = {"indptr": indptr, "indices": indices, "data": data, "nnz": int(out_nnz.value), "val_dtype": np_dtype_of(out.dtype),
+           "blocks": table, "drawn": None}
     if d_drawn is not None:
         res["drawn"] = d_drawn.download()[:nnz].copy()
     return res
