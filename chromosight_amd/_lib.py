@@ -240,6 +240,7 @@ _PROTOTYPES = {
     "cs_last_kernel": (C.c_int, [C.c_void_p]),
     "cs_last_dense_waves": (C.c_int, [C.c_void_p]),
     "cs_dense_tile_walk": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "cs_dense8_offsets": (C.c_int, [C.c_longlong, C.c_longlong, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "cs_ctx_set_range_check": (C.c_int, [C.c_void_p, C.c_int32]),
     "cs_ctx_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "cs_ctx_destroy": (None, [C.c_void_p]),

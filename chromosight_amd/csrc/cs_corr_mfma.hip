@@ -991,8 +991,13 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
         // The headline configuration -- 16-byte transfers, a 17 x 17 template whose rows mirror -- runs the same tile with eight
         // waves of at most 128 registers, four per SIMD (cs_corr_mfma_dense8.inc); CHROMOSIGHT_HIP_MFMA_WAVES4 keeps the 4-wave
         // instance, which serves every other dense call.
-        const bool waves8 = vec4 && A.mfma_rsym != 0 && A.km == 17 && A.kn == 17 && !waves4;
-        const void* kd = waves8 ? (const void*)corr_mfma_dense8_kernel
+        // Its lane offsets are 32-bit (Dense8Offsets): a pitch beyond them keeps the 4-wave instance too.
+        const bool waves8 = vec4 && A.mfma_rsym != 0 && A.km == 17 && A.kn == 17 && !waves4 &&
+                            Dense8Offsets::fits(D.ld_in, D.ld_out, D.out_is_f64 ? 8 : 4);
+        typedef void (*dense8_kernel_t)(const MfmaDenseArgs);
+        const dense8_kernel_t kd8 = D.xcorr_only ? (D.out_is_f64 ? corr_mfma_dense8_kernel<true, true> : corr_mfma_dense8_kernel<true, false>)
+                                                 : (D.out_is_f64 ? corr_mfma_dense8_kernel<false, true> : corr_mfma_dense8_kernel<false, false>);
+        const void* kd = waves8 ? (const void*)kd8
                          : vec4 ? (const void*)corr_mfma_dense_kernel<true, false> : (const void*)corr_mfma_dense_kernel<false, false>;
         hipError_t e2 = allow_big_lds(kd);
         if (e2 != hipSuccess) return (int)e2;
@@ -1001,7 +1006,7 @@ int launch_corr_mfma_f32(CorrArgs<float>& A, const MfmaWeights& E, hipStream_t s
         D.xcd_order |= dense_tile_skew(A.tiles_x, blocks, (D.xcd_order & 1) && grid % 8 == 0 ? grid / 8 : grid) << 1;
         if (dense_waves) *dense_waves = waves8 ? 8 : 4;
         if (waves8) {
-            hipLaunchKernelGGL(corr_mfma_dense8_kernel, dim3((unsigned)grid), dim3(512), MF8_LAUNCH, stream, D);
+            hipLaunchKernelGGL(kd8, dim3((unsigned)grid), dim3(512), MF8_LAUNCH, stream, D);
             return (int)hipGetLastError();
         }
         if (vec4) hipLaunchKernelGGL((corr_mfma_dense_kernel<true, false>), dim3((unsigned)grid), dim3(256), (MFD_LAUNCH_EXTRA ? MFD_SMEM_REG + MFD_LAUNCH_EXTRA : MFD_SMEM), stream, D);
@@ -1100,4 +1105,19 @@ extern "C" int cs_dense_tile_walk(int tiles_x, int n_tiles, int grid, int xcd_or
     for (; !walk.done(); walk.advance(), ++n)
         if (n < cap) walk.origin(row_begin, i0[n], j0[n]);
     return n;
+}
+
+// The 8-wave dense instance's tile-invariant lane offsets, by the helper the kernel itself uses (Dense8Offsets): fetch[4 t + k] is
+// the byte offset of piece k of thread t from a tile's first staged pixel, store[t] that of thread t's plain store from the tile's
+// first output pixel, both modulo 2^32.  Returns the launcher's route condition -- 1: the offsets fit, 0: the pitches keep the
+// 4-wave instance -- or -1 on bad arguments.
+extern "C" int cs_dense8_offsets(long long ld_in, long long ld_out, int out_is_f64, unsigned* fetch, unsigned* store)
+{
+    if (ld_in <= 0 || ld_out <= 0 || !fetch || !store) return -1;
+    const unsigned elem = out_is_f64 ? 8 : 4;
+    for (int t = 0; t < 512; ++t) {
+        for (int k = 0; k < 4; ++k) fetch[4 * t + k] = cs::Dense8Offsets::fetch(t, k, (unsigned)ld_in);
+        store[t] = cs::Dense8Offsets::store(t, (unsigned)ld_out, elem);
+    }
+    return cs::Dense8Offsets::fits(ld_in, ld_out, (int)elem) ? 1 : 0;
 }

@@ -13,7 +13,9 @@
 //
 // Twice the waves repeat what a wave does per tile beside its MFMAs, so that part is kept short (DESIGN.md "The 8-wave dense
 // kernel: what each wave repeats per tile"): the tile walk is carried without divisions (DenseTileWalk), no staging lane is
-// masked, the wave maximum runs on bit patterns (wave_max_bits).  None of it changes a value.
+// masked, the wave maximum runs on bit patterns (wave_max_bits).  What a launch fixes -- plain cross-correlation or coefficient,
+// float32 or float64 output -- is a template parameter, and an inner tile's transfers and stores go through a buffer descriptor
+// whose base the scalar unit forms per tile, with 32-bit lane offsets formed once (Dense8Offsets).  None of it changes a value.
 
 constexpr int MF8_ROWS_PER_THREAD = 7;          // staging: 480 threads = 40 column pairs x 12 row groups
 constexpr int MF8_RED = MFD_WL + 18 * 1024;     // four planes, 9 tail + 9 head rows of weights, then the 8 wave maxima
@@ -79,6 +81,36 @@ struct DenseTileWalk {
     }
 };
 
+// What does not change from tile to tile in the addresses of an inner tile: a lane's byte offsets from the tile's first staged
+// pixel (transfers) and from its first output pixel (stores).  Per tile only a uniform 64-bit base remains, which the scalar
+// unit forms; base and offset meet in a buffer descriptor (`buffer_load_dwordx4 ... offen lds`, `buffer_store_dwordx4 ... offen`:
+// the form the compiler has for scalar base + 32-bit lane offset with 16-byte pieces; a global_load_lds is given a 64-bit
+// lane address whatever the source says).  The offsets are 32-bit: fits() is the launcher's route condition.
+struct Dense8Offsets {
+    // piece k of thread t is piece p = t + 512 k of the tile's 1600 (80 rows x 20 pieces of 16 bytes): row p / 20, piece p % 20
+    __host__ __device__ static unsigned fetch(int t, int k, unsigned ld_in)
+    {
+        const unsigned p = (unsigned)t + 512u * (unsigned)k, r = p / 20u, c = p - 20u * r;
+        return (r * ld_in + 4u * c) * 4u;
+    }
+    // the plain store of thread t (see emit): row 16 (w & 3) + (n & 7) of the tile, columns 32 (w >> 2) + (n < 8 ? 0 : 16) + 4 g;
+    // its second store lies 8 rows below
+    __host__ __device__ static unsigned store(int t, unsigned ld_out, unsigned elem)
+    {
+        const unsigned lane = (unsigned)t & 63u, wv = (unsigned)t >> 6, n = lane & 15u, g = lane >> 4;
+        return ((16u * (wv & 3u) + (n & 7u)) * ld_out + 32u * (wv >> 2) + (n < 8u ? 0u : 16u) + 4u * g) * elem;
+    }
+    // bytes a tile's transfers (80 rows) and plain stores (64 rows) span from their bases: the descriptors' ranges
+    __host__ __device__ static unsigned fetch_span(unsigned ld_in) { return ((MF_R - 1) * ld_in + MF_R) * 4u; }
+    __host__ __device__ static unsigned store_span(unsigned ld_out, unsigned elem) { return ((MF_T - 1) * ld_out + MF_T) * elem; }
+    // every offset and span stays below 2^31 (80 rows of either pitch; elem: bytes of an output value)
+    __host__ __device__ static bool fits(long long ld_in, long long ld_out, int elem)
+    {
+        const long long lim = 1LL << 31;
+        return ld_in > 0 && ld_out > 0 && ld_in < lim && ld_out < lim && 80 * ld_in * 4 < lim && 80 * ld_out * elem < lim;
+    }
+};
+
 // maximum over the wave of the bit patterns of non-negative floats, which order as unsigned integers; valid in lane 63.  The
 // integer maximum takes its DPP operand directly: no canonicalisation and no separate move (wave_max_nonneg has both).
 __device__ __forceinline__ unsigned wave_max_bits(unsigned v)
@@ -94,6 +126,8 @@ __device__ __forceinline__ unsigned wave_max_bits(unsigned v)
     return v;
 }
 
+// XCORR: plain cross-correlation (A.xcorr_only); F64: float64 output (A.out_is_f64).  The launcher picks the instance.
+template <bool XCORR, bool F64>
 __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDenseArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -147,28 +181,29 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
     // LDS-DMA of one tile's 80 x 80 pixels in 16-byte pieces (20 per row): a wave-wide transfer moves 64 consecutive pieces, wave
     // w issues the transfers w, w + 8, ...; a lane's piece advances by 512 pieces -- 25 rows and 12 pieces -- per step.
     const int wv_u = __builtin_amdgcn_readfirstlane(wv);
+    // a lane's pieces of an inner tile, as byte offsets from the tile's first staged pixel (the fourth: wave 0 only)
+    unsigned f_off[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f_off[k] = Dense8Offsets::fetch(tid, k, (unsigned)A.ld_in);
+    const unsigned f_span = Dense8Offsets::fetch_span((unsigned)A.ld_in);
     auto fetch = [&](int I0, int J0, bool inside) {
         const int P0 = I0 - KH, Q0 = J0 - KH;
-        const int e0 = 64 * wv_u + lane;
-        int r = e0 / 20, c = e0 - r * 20;
         const lds_char* dst = (const lds_char*)(raw) + 1024 * wv_u;
         if (inside) {
-            // inner tiles (nearly all): no clamp can bite, a piece's address is one base + r ld + 4 c
-            const float* src = A.sig + ((long long)P0 + r - A.row0_in) * A.ld_in + Q0 + 4 * c;
-            const long long step_r = 25 * A.ld_in + 48, wrap = A.ld_in - 80;
-#pragma unroll 1
-            for (int i = wv_u; i < 25; i += 8) {
-                __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-                dst += 8192;
-                c += 12;
-                src += step_r;
-                if (c >= 20) {
-                    c -= 20;
-                    src += wrap;
-                }
-            }
+            // inner tiles (nearly all): no clamp can bite, a piece's address is the tile's base -- uniform: scalar -- plus
+            // the lane's offset of the prologue; the descriptor's range is the tile's 80 rows
+            const float* base = A.sig + ((long long)P0 - A.row0_in) * A.ld_in + Q0;
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)f_span, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + 8192 * k), 16, (int)f_off[k], 0, 0, 0);
+            static_assert(7 + 8 * 2 < 25 && 1 + 8 * 3 >= 25, "three transfers per wave, a fourth for wave 0");
+            if (wv_u == 0)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(dst + 8192 * 3), 16, (int)f_off[3], 0, 0, 0);
             return;
         }
+        const int e0 = 64 * wv_u + lane;
+        int r = e0 / 20, c = e0 - r * 20;
         // clamped addresses; the reader masks what lies outside (ns and the first staged column are multiples of 4: a piece
         // lies inside a row or outside it, never across its end)
 #pragma unroll 1
@@ -187,6 +222,11 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         }
     };
 
+    // a lane's plain store of a tile, as a byte offset from the tile's first output pixel
+    constexpr int ELEM = F64 ? 8 : 4;
+    const unsigned s_off = Dense8Offsets::store(tid, (unsigned)A.ld_out, ELEM);
+    const unsigned s_span = Dense8Offsets::store_span((unsigned)A.ld_out, ELEM);
+
     // Epilogue of one tile (lane = row n of the wave's 16, columns wc0 + 16 c + 4 g + v), run one iteration late: its stores have
     // the whole next tile to retire before the `vmcnt(0)` that awaits the DMA.  The arithmetic is the unmasked epilogue of
     // cs_corr_mfma_body.inc, statement for statement.
@@ -198,7 +238,7 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
                            (!A.sym_upper || J0 - (I0 + MF_T - 1) >= 0);
         const int i = I0 + wr0 + n;
         f4 rv[2];
-        bool lean = !A.xcorr_only && !(A.ks.cand_cmin > 0.0f);
+        bool lean = !XCORR && !(A.ks.cand_cmin > 0.0f);
         if (lean) {
             const KernelStats<float>& KS = A.ks;
             const float inv_u = __uint_as_float((254u << 23) - __float_as_uint(unscale));          // 2^ex, exact
@@ -234,8 +274,8 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
                 const float cs = acc[c][v] * u_cs;
                 const float s1 = S1[c][v] * unscale;
                 const float s2 = (S2[c][v] * u_s2) * unscale;
-                rv[c][v] = A.xcorr_only ? (fabsf(cs) < A.ks.thr ? 0.0f : cs)            // detection.py:716-722
-                                        : cand_range_guard(pearson_nomask_lean(cs, s1, s2, A.ks), s2, unscale, A.ks);
+                if constexpr (XCORR) rv[c][v] = fabsf(cs) < A.ks.thr ? 0.0f : cs;       // detection.py:716-722
+                else rv[c][v] = cand_range_guard(pearson_nomask_lean(cs, s1, s2, A.ks), s2, unscale, A.ks);
             }
         }
         if (plain) {
@@ -252,21 +292,24 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
                 s0[v] = top8 ? rv[0][v] : theirs;          // rows 0 .. 7:  columns 4 g (own) | 16 + 4 g (of lane n - 8)
                 s1[v] = top8 ? theirs : rv[1][v];          // rows 8 .. 15: columns 4 g (of lane n + 8) | 16 + 4 g (own)
             }
-            const long long r_idx = ((long long)(I0 + wr0 + (n & 7)) - A.row0_out) * A.ld_out + J0 + wc0 + (top8 ? 0 : 16) + 4 * g;
-            if (A.out_is_f64) {
+            // the tile's first output pixel -- uniform: scalar -- in a descriptor over the tile's 64 rows; the lane's offset is
+            // that of the prologue, the 8 rows between its two stores the instruction's scalar offset
+            typedef unsigned u4 __attribute__((ext_vector_type(4)));
+            char* const ob = reinterpret_cast<char*>(A.out) + (((long long)I0 - A.row0_out) * A.ld_out + J0) * ELEM;
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (int)s_span, 0x00020000);
+            const int down8 = 8 * (int)A.ld_out * ELEM;
+            if constexpr (F64) {
                 typedef double d2 __attribute__((ext_vector_type(2)));
-                double* od = reinterpret_cast<double*>(A.out) + r_idx;
                 d2 a, b;
                 a[0] = s0[0]; a[1] = s0[1]; b[0] = s0[2]; b[1] = s0[3];
-                *reinterpret_cast<d2*>(od) = a;
-                *reinterpret_cast<d2*>(od + 2) = b;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, a), ro, (int)s_off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, b), ro, (int)s_off + 16, 0, 0);
                 a[0] = s1[0]; a[1] = s1[1]; b[0] = s1[2]; b[1] = s1[3];
-                *reinterpret_cast<d2*>(od + 8 * A.ld_out) = a;
-                *reinterpret_cast<d2*>(od + 8 * A.ld_out + 2) = b;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, a), ro, (int)s_off, down8, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, b), ro, (int)s_off + 16, down8, 0);
             } else {
-                float* of = reinterpret_cast<float*>(A.out) + r_idx;
-                *reinterpret_cast<f4*>(of) = s0;
-                *reinterpret_cast<f4*>(of + 8 * A.ld_out) = s1;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, s0), ro, (int)s_off, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, s1), ro, (int)s_off, down8, 0);
             }
         } else {
             // tiles on the rim of the map, of the row window, of the valid area or across the diagonal: pixel by pixel
@@ -281,7 +324,7 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
                     if (A.sym_upper) z = z | ((j - i) < 0);
                     if (i < A.row_end && j < A.ns) {
                         const float val = z ? 0.0f : rv[c][v];
-                        if (A.out_is_f64) reinterpret_cast<double*>(A.out)[o_idx + 16 * c + v] = (double)val;
+                        if constexpr (F64) reinterpret_cast<double*>(A.out)[o_idx + 16 * c + v] = (double)val;
                         else reinterpret_cast<float*>(A.out)[o_idx + 16 * c + v] = val;
                     }
                 }
@@ -414,10 +457,11 @@ __global__ __launch_bounds__(512, 4) void corr_mfma_dense8_kernel(const MfmaDens
         // ---- box sums: horizontal pass over the wave's 32 input rows, the partial sums split again and fed to the vertical
         //      pass as they lie (ones_p).  4 steps (2 column tiles x {x, x^2}); the fragments of step t + 1 are loaded before
         //      the conversions of step t.
-        f4 S1[2], S2[2];
+        f4 S1[2], S2[2];                         // (every one of them is the result of a step below)
+        if constexpr (XCORR) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) S1[c] = S2[c] = zero4;
-        if (!A.xcorr_only) {
+            for (int c = 0; c < 2; ++c) S1[c] = S2[c] = zero4;
+        } else {
             auto hfrag = [&](int t, h8 (&f)[4]) {
                 const int c = t >> 1;
                 const char* ph = (t & 1) ? pl_qh : pl_xh;

@@ -106,6 +106,12 @@ int cs_last_dense_waves(const cs_ctx* ctx);
  * `row_begin`.  Fills at most `cap` entries of i0 / j0 and returns the number of tiles of the workgroup, -1 on bad arguments.
  * Needs no device. */
 int cs_dense_tile_walk(int tiles_x, int n_tiles, int grid, int xcd_order, int row_begin, int block, int* i0, int* j0, int cap);
+/* The tile-invariant lane offsets of the 8-wave instance, from the helper the kernel uses, for an input pitch `ld_in` and an output
+ * pitch `ld_out` (elements) of float32 or float64 values: fetch[4 t + k] is the byte offset of the 16-byte piece k of thread t
+ * (piece t + 512 k of a tile's 80 rows x 20) from the tile's first staged pixel, store[t] the byte offset of thread t's plain store
+ * from the tile's first output pixel, both modulo 2^32 (512 threads).  Returns 1 when the pitches are served by the 8-wave
+ * instance (80 rows of either pitch stay below 2^31 bytes), 0 when they keep the 4-wave one, -1 on bad arguments.  Needs no device. */
+int cs_dense8_offsets(long long ld_in, long long ld_out, int out_is_f64, unsigned* fetch, unsigned* store);
 /* Range guard of the device entries (off by default).  The reference sums every window on its own
  * (detection.py:1002-1018) and zeroes exactly the windows that hold a non-finite pixel (:1088-1101); the device kernels
  * keep running box sums and square in float32, so a DEVICE-RESIDENT map handed to cs_normxcorr2 must be finite and, for
