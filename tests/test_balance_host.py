@@ -18,7 +18,8 @@ GOLDEN = ROOT / "tests" / "golden"
 def ice_restatement(cool, cis_only=True, mad_max=5, min_nnz=10, min_count=0, ignore_diags=2, tol=1e-5, max_iters=200,
                     rescale_marginals=True):
     """cooler.balance_cooler (store=False) in numpy: filters, initial bias, MAD filter, then the ICE loop per span (a chromosome
-    with cis_only, else the genome).  Returns (weights, info) with per-span lists iterations, var, scale, converged."""
+    with cis_only, else the genome).  Returns (weights, info) with per-span lists iterations, var, scale, converged, and
+    variances: per span the list of the variance of every iteration."""
     off = np.asarray(cool["chrom_offset"], dtype=np.int64)
     n = int(off[-1])
     b1 = np.asarray(cool["bin1_id"], dtype=np.int64)
@@ -52,11 +53,11 @@ def ice_restatement(cool, cis_only=True, mad_max=5, min_nnz=10, min_count=0, ign
             dev = np.median(np.abs(logs - med))
             bias[scaled < np.exp(med - mad_max * dev)] = 0
     spans = list(zip(off[:-1], off[1:])) if cis_only else [(0, n)]
-    info = {"iterations": [], "var": [], "scale": [], "converged": []}
+    info = {"iterations": [], "var": [], "scale": [], "converged": [], "variances": []}
     for lo, hi in spans:
         a, b = np.searchsorted(b1, [lo, hi]) if cis_only else (0, b1.size)      # (the table is sorted by bin1)
         s1, s2, sv = b1[a:b] - lo, b2[a:b] - lo, v[a:b]
-        it, conv, var, nz = 0, False, 0.0, np.zeros(0)
+        it, conv, var, nz, history = 0, False, 0.0, np.zeros(0), []
         while it < max_iters:
             it += 1
             x = sv * bias[lo + s1] * bias[lo + s2]
@@ -65,11 +66,13 @@ def ice_restatement(cool, cis_only=True, mad_max=5, min_nnz=10, min_count=0, ign
             if nz.size == 0:
                 bias[lo:hi] = np.nan
                 var, conv = 0.0, True
+                history.append(var)
                 break
             m = m / nz.mean()
             m[m == 0] = 1
             bias[lo:hi] /= m
             var = nz.var()
+            history.append(var)
             if var < tol:
                 conv = True
                 break
@@ -78,7 +81,7 @@ def ice_restatement(cool, cis_only=True, mad_max=5, min_nnz=10, min_count=0, ign
         b[b == 0] = np.nan
         if rescale_marginals:
             bias[lo:hi] = b / np.sqrt(scale)
-        for k, x in zip(("iterations", "var", "scale", "converged"), (it, var, scale, conv)):
+        for k, x in zip(("iterations", "var", "scale", "converged", "variances"), (it, var, scale, conv, history)):
             info[k].append(x)
     return bias, info
 
