@@ -324,6 +324,10 @@ _PROTOTYPES = {
                                     C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "cs_inflate_max_chunk_bytes": (C.c_int64, []),
+    "cs_bgzf_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_int64)]),
+    "cs_bgzf_max_block_bytes": (C.c_int64, []),
     "cs_table_from_columns_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64,
                                               C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(CsTableReport)]),
     "cs_table_from_columns_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32]),

@@ -218,14 +218,15 @@ class TextReport(NamedTuple):
     reason: int
 
 
-def parse_pairs_text(dev, text, columns, width, names, timings=None):
+def parse_pairs_text(dev, text, columns, width, names, timings=None, nbytes=None, offset=0):
     """One piece of the body of a .pairs file parsed on `dev` (cs_pairs_text_count / cs_pairs_text_parse).  text: a bytes-like object,
     uploaded here, or a device buffer of uint8 that holds exactly the text (never written); columns: the 0-based fields of chr1, pos1,
     chr2, pos2; width: the most fields a line may have; names: the chromosome names in genome order.  Returns (columns, n, report):
     the four resident columns as pairs_csr_resident takes them (a list; int32, int64, int32, int64, n entries in line order), the
     number of lines and a TextReport.  With a flagged line the columns hold nothing of use.  ValueError for columns that are not four
     distinct fields below width, a name given twice and a text of 2^31 - 1 lines or more.  timings: a dict that receives the seconds
-    of `upload`, `count` and `parse` (each ends in a synchronisation)."""
+    of `upload`, `count` and `parse` (each ends in a synchronisation).  nbytes, offset: of a device buffer, the text is the nbytes
+    bytes (default: all behind offset) from byte `offset`, a multiple of 16; the rest of the buffer is not read."""
     import time
     encoded = [str(name).encode("utf-8") for name in names]
     offsets = np.zeros(len(encoded) + 1, dtype=np.int64)
@@ -238,18 +239,22 @@ def parse_pairs_text(dev, text, columns, width, names, timings=None):
         if not isinstance(text, DeviceBuffer):
             host = np.frombuffer(text, dtype=np.uint8)
             text = dev.to_device(host) if host.size else dev.empty(0, np.uint8)
-        nbytes = int(text.nbytes)
+        offset = int(offset)
+        nbytes = int(text.nbytes) - offset if nbytes is None else int(nbytes)
+        if offset < 0 or offset % 16 or nbytes < 0 or offset + nbytes > int(text.nbytes):
+            raise ValueError(f"a text of {nbytes} bytes at offset {offset} of a buffer of {int(text.nbytes)}: it must lie inside, at a multiple of 16")
+        at = text.ptr + offset
         t1 = time.perf_counter()
         n_lines = C.c_int64(0)
         report = CsPairsTextReport()
         try:
-            dev._check(dev.lib.cs_pairs_text_count(dev.ctx, None, text.ptr, nbytes, C.byref(n_lines)))
+            dev._check(dev.lib.cs_pairs_text_count(dev.ctx, None, at, nbytes, C.byref(n_lines)))
             n = int(n_lines.value)
             t2 = time.perf_counter()
             if n > MAX_CHUNK_PAIRS:
                 raise ValueError(f"a text of {n} lines: more than 2^31 - 2 are not parsed in one call")
             cols = [dev.empty(max(n, 1), dtype) for dtype in (np.int32, np.int64, np.int32, np.int64)]
-            dev._check(dev.lib.cs_pairs_text_parse(dev.ctx, None, text.ptr, nbytes, C.byref(fmt), *[c.ptr for c in cols], n, C.byref(report)))
+            dev._check(dev.lib.cs_pairs_text_parse(dev.ctx, None, at, nbytes, C.byref(fmt), *[c.ptr for c in cols], n, C.byref(report)))
         except NotImplementedError as exc:          # CS_ERR_UNSUPPORTED: a limit of the kernel, not a missing feature
             raise ValueError(str(exc)) from None
         t3 = time.perf_counter()
@@ -356,19 +361,221 @@ def _skip_header(read, n_lines, path):
     return buf[at:]
 
 
-def parsed_pieces(pairs_file, piece_bytes, parse, timings=None):
+class BgzfBlock(NamedTuple):
+    """One member of a BGZF file: where it starts, where its raw deflate body lies, and the size of its text."""
+    file_offset: int
+    body_offset: int
+    body_bytes: int
+    isize: int
+
+
+BGZF_MAX_ISIZE = 65536
+
+
+def bgzf_blocks(buf):
+    """The members of a bgzip-compressed file, one BgzfBlock after the other, walked over `buf`: the file's bytes as anything with the
+    buffer protocol (a mapping of the file; only the header and the trailer of a member are read).  pipeline.DeviceInflateRefused (a
+    ValueError) at the first thing that is not a qualifying member directly behind the one before it: a member has the magic 1f 8b,
+    method 8 and the flags 4 (an extra field and nothing else), exactly one subfield 'BC' of 2 bytes among the subfields that fill its
+    extra field (it holds the member's size - 1), ends inside the file and holds at most 65 536 bytes of text.  The 28-byte end marker
+    is a member without text; a file without it, and a file without bytes, is walked all the same.  Plain gzip output, a member with a
+    name, a comment or a header CRC, zero padding between members and trailing bytes are refused."""
+    import struct
+    from .pipeline import DeviceInflateRefused
+    view = memoryview(buf)
+    try:
+        size, at, k = view.nbytes, 0, 0
+        while at < size:
+            where = f"member {k} at byte {at}"
+            if size - at < 12:
+                raise DeviceInflateRefused(f"{where}: {size - at} bytes are no gzip header")
+            magic, method, flags, xlen = struct.unpack_from("<HBB6xH", view, at)
+            if magic != 0x8B1F or method != 8:
+                raise DeviceInflateRefused(f"{where}: not a gzip member")
+            if flags != 4:
+                raise DeviceInflateRefused(f"{where}: gzip flags {flags:#04x}, a BGZF member has an extra field and nothing else (0x04)")
+            if at + 12 + xlen > size:
+                raise DeviceInflateRefused(f"{where}: the extra field leaves the file")
+            sub, end, bsize = at + 12, at + 12 + xlen, None
+            while sub < end:
+                if end - sub < 4:
+                    raise DeviceInflateRefused(f"{where}: the subfields do not fill the extra field")
+                si1, si2, slen = struct.unpack_from("<BBH", view, sub)
+                if sub + 4 + slen > end:
+                    raise DeviceInflateRefused(f"{where}: a subfield leaves the extra field")
+                if (si1, si2) == (66, 67):
+                    if slen != 2 or bsize is not None:
+                        raise DeviceInflateRefused(f"{where}: more than one 'BC' subfield, or one that is not 2 bytes")
+                    bsize, = struct.unpack_from("<H", view, sub + 4)
+                sub += 4 + slen
+            if bsize is None:
+                raise DeviceInflateRefused(f"{where}: no 'BC' subfield: gzip, not bgzip")
+            total = bsize + 1
+            if total < 12 + xlen + 8:
+                raise DeviceInflateRefused(f"{where}: a member of {total} bytes does not hold its own header and trailer")
+            if at + total > size:
+                raise DeviceInflateRefused(f"{where}: the member ({total} bytes) leaves the file: truncated")
+            isize, = struct.unpack_from("<I", view, at + total - 4)
+            if isize > BGZF_MAX_ISIZE:
+                raise DeviceInflateRefused(f"{where}: {isize} bytes of text, a BGZF member holds at most {BGZF_MAX_ISIZE}")
+            yield BgzfBlock(at, at + 12 + xlen, total - 12 - xlen - 8, isize)
+            at += total
+            k += 1
+    finally:
+        view.release()
+
+
+def _corrupt_member(path, k, block, status):
+    """engine.CorruptChunks for member k of a file; .block and .file_offset name it, .status holds its code (an index into
+    engine.BGZF_STATUS; -1 for status None: a member of the header, which the host's zlib inflates and did not take)."""
+    from .engine import BGZF_STATUS, CorruptChunks
+    if status is None:
+        why, status = "the host's zlib does not take it", -1
+    else:
+        why = f"{BGZF_STATUS[status] if 0 <= status < len(BGZF_STATUS) else 'unknown status'} (status {status})"
+    exc = CorruptChunks(f"{path}: BGZF member {k} at byte {block.file_offset} does not decode: {why}", np.asarray([status]))
+    exc.block, exc.file_offset = k, block.file_offset
+    return exc
+
+
+def _device_inflated_pieces(pf, mm, piece_bytes, dev, timings):
+    """The body of a bgzip-compressed .pairs.gz (pf: its io.PairsFile; mm: a mapping of the file) as text on the device, piece by piece:
+    yields (buffer, start, nbytes) -- a DeviceBuffer of uint8 and the span of it to parse, which starts at a multiple of 16 and ends
+    behind a line end, or at the end of the file.  The header's members are inflated on the host (zlib, raw deflate) to find the member
+    and the offset in it where the body starts; from there a piece is as many members as keep carry + their text within piece_bytes,
+    one at the least.  Their bytes go to the device as they are in the file and are inflated there (cs_bgzf_inflate) behind the carry:
+    the text behind the last '\\n' of the piece before (fetched from the device and uploaded again: a fraction of a line as a rule; a
+    piece without a line end whole).  In the first piece the member is placed so that the body starts at a multiple of 16."""
+    import time
+    from . import engine
+
+    def clocked(key, t0):
+        if timings is not None:
+            timings[key] = timings.get(key, 0.0) + time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    blocks = list(bgzf_blocks(mm))
+    clocked("read", t0)
+    # the header: member after member through the host's zlib until its lines are read
+    state = {"next": 0}
+
+    def read_header(_n):
+        while state["next"] < len(blocks):
+            k = state["next"]
+            b = blocks[k]
+            state["next"] += 1
+            inflater = zlib.decompressobj(-15)
+            end = b.body_offset + b.body_bytes
+            try:
+                text = inflater.decompress(mm[b.body_offset:end])
+                whole = inflater.eof and not inflater.unused_data and len(text) == b.isize and \
+                    zlib.crc32(text) == int.from_bytes(mm[end:end + 4], "little")
+            except zlib.error:
+                whole = False
+            if not whole:
+                raise _corrupt_member(pf.path, k, b, None)
+            if text:
+                return text
+        return b""
+
+    t0 = time.perf_counter()
+    rest = _skip_header(read_header, pf.header_lines, pf.path)
+    clocked("read", t0)
+    k = state["next"]                               # the next member to inflate, and where in it the body starts
+    skip = 0
+    if rest:
+        k -= 1
+        skip = blocks[k].isize - len(rest)
+    del rest
+    carry = np.empty(0, dtype=np.uint8)
+    while k < len(blocks) or carry.size:
+        t0 = time.perf_counter()
+        first = k
+        room = int(carry.size) - skip               # (the header's part of the first member is no text of the piece)
+        while k < len(blocks) and (k == first or room + blocks[k].isize <= piece_bytes):
+            room += blocks[k].isize
+            k += 1
+        mine = blocks[first:k]
+        pad = -skip % 16
+        start = pad + skip
+        out_offsets = np.cumsum([pad + int(carry.size)] + [b.isize for b in mine], dtype=np.int64)
+        end = int(out_offsets[-1])
+        clocked("cut", t0)
+        with dev.lock:
+            t0 = time.perf_counter()
+            text = dev.empty(max(end, 1), np.uint8)
+            if carry.size:
+                dev._check(dev.lib.cs_memcpy_h2d(dev.ctx, text.ptr, carry.ctypes.data, int(carry.size), None))
+            last = -1
+            if mine:
+                lo, hi = mine[0].file_offset, mine[-1].body_offset + mine[-1].body_bytes + 8
+                span = np.frombuffer(mm, dtype=np.uint8, count=hi - lo, offset=lo)
+                try:
+                    d_file = dev.to_device(span)
+                finally:
+                    del span                        # (no view of the mapping outlives this block: it could not be closed)
+                clocked("upload", t0)
+                t0 = time.perf_counter()
+                try:
+                    _, last = engine.run_bgzf_inflate(dev, d_file, hi - lo, [b.body_offset - lo for b in mine], [b.body_bytes for b in mine],
+                                                      out_offsets[:-1], [b.isize for b in mine], text, end)
+                except engine.CorruptChunks as exc:
+                    bad = int(np.flatnonzero(exc.status)[0])
+                    raise _corrupt_member(pf.path, first + bad, mine[bad], int(exc.status[bad])) from None
+                del d_file
+                clocked("inflate", t0)
+            else:
+                clocked("upload", t0)
+            t0 = time.perf_counter()
+            if k >= len(blocks):                    # the last piece: to its end, with or without a final line end
+                cut, carry = end, carry[:0]
+            else:
+                cut = last + 1 if last >= start else start
+                carry = np.empty(end - cut, dtype=np.uint8)
+                if carry.size:
+                    dev._check(dev.lib.cs_memcpy_d2h(dev.ctx, carry.ctypes.data, text.ptr + cut, int(carry.size), None))
+            clocked("cut", t0)
+        skip = 0
+        if cut > start:
+            yield text, start, cut - start
+        del text
+
+
+def parsed_pieces(pairs_file, piece_bytes, parse, timings=None, inflate="host", dev=None):
     """The body of a .pairs file, piece by piece (text_pieces; .gz: inflated on the host as a stream, GzipSource), through
     parse(piece, columns, width, names) -> (columns, n, TextReport): yields (columns, n) per piece.  pairs_file: the io.PairsFile of
     the file -- its header pass gives the columns, the width and the number of header lines, which are skipped here.
     pipeline.DevicePairsRefused (a ValueError) for the first flagged line, named by its 1-based number in the file: the header's
     lines + the lines of the pieces before + its index + 1.  timings: a dict that receives the seconds spent in `read` and in
-    `cut` (finding the line ends, carrying and joining)."""
+    `cut` (finding the line ends, carrying and joining).
+    inflate="device" (a .gz written by bgzip; `dev` is needed): the members of the file are inflated on the device
+    (_device_inflated_pieces), the host never sees the body's text, and parse receives (buffer, columns, width, names, start, nbytes)
+    -- the text is nbytes bytes of the device buffer from `start`.  pipeline.DeviceInflateRefused for a file that is not BGZF
+    throughout, before anything is parsed; engine.CorruptChunks for the first member that does not decode.  timings gains `inflate`."""
+    import mmap
+    import os
     import time
     from .pipeline import DevicePairsRefused
     pf = pairs_file
     width = max(pf.width, max(pf.columns) + 1)      # (a short first line: the parser flags it, as the host refuses it)
     names = list(pf.chromsizes)
     lines_before = pf.header_lines
+    if inflate == "device":
+        with open(pf.path, "rb") as handle:
+            mm = mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(handle.fileno()).st_size else b""
+            try:
+                for text, start, nbytes in _device_inflated_pieces(pf, mm, piece_bytes, dev, timings):
+                    cols, n, report = parse(text, pf.columns, width, names, start, nbytes)
+                    if report.first_flagged >= 0:
+                        raise DevicePairsRefused(f"{pf.path}, line {lines_before + report.first_flagged + 1}: "
+                                                 f"{FLAG_REASONS.get(report.reason, f'reason {report.reason}')}")
+                    del text
+                    yield cols, n
+                    lines_before += n
+            finally:
+                if mm:
+                    mm.close()
+        return
     with open(pf.path, "rb") as handle:
         read = GzipSource(handle).read if pf.path.endswith(".gz") else handle.read
         if timings is not None:
@@ -397,14 +604,15 @@ def parsed_pieces(pairs_file, piece_bytes, parse, timings=None):
             lines_before += n
 
 
-def pairs_file_device(pairs_file, binsize, zero_based=False, piece_bytes=None, dev=None, timings=None):
+def pairs_file_device(pairs_file, binsize, zero_based=False, piece_bytes=None, dev=None, timings=None, inflate="host"):
     """DeviceCool.from_pairs_file on its device route: the table of a .pairs file (pairs_file: its io.PairsFile) whose text is parsed
     on the device.  Every piece of parsed_pieces goes through parse_pairs_text, is binned (pairs_csr_resident) and merged into the
     running table as pairs_device merges a chunk; the binning is exact, so the table is that of pairs_device over the host reader's
     chunks, bit for bit, for every piece_bytes (default PIECE_BYTES).  The peak in HBM is a piece's text + its columns (24 bytes per
     line), and, once the text is released, what pairs_device states for a chunk of that many pairs.  pipeline.DevicePairsRefused
     for a flagged line; ValueError as pairs_csr for pairs outside the genome.  timings: a dict that receives the seconds of `read`,
-    `cut`, `upload`, `count`, `parse` and `bin` (binning and merge)."""
+    `cut`, `upload`, `count`, `parse` and `bin` (binning and merge).  inflate: "host", or "device" for a .gz that bgzip wrote, whose
+    members are then inflated in HBM too (parsed_pieces; timings gains `inflate`)."""
     import time
     dev = dev or get_device()
     piece_bytes = PIECE_BYTES if piece_bytes is None else int(piece_bytes)
@@ -413,10 +621,10 @@ def pairs_file_device(pairs_file, binsize, zero_based=False, piece_bytes=None, d
     geo = bin_geometry(pairs_file.chromsizes, binsize)
     running = _RunningTable(geo, dev)
 
-    def parse(piece, columns, width, names):
-        return parse_pairs_text(dev, piece, columns, width, names, timings=timings)
+    def parse(piece, columns, width, names, offset=0, nbytes=None):
+        return parse_pairs_text(dev, piece, columns, width, names, timings=timings, nbytes=nbytes, offset=offset)
 
-    for cols, n in parsed_pieces(pairs_file, piece_bytes, parse, timings):
+    for cols, n in parsed_pieces(pairs_file, piece_bytes, parse, timings, inflate=inflate, dev=dev):
         t0 = time.perf_counter()
         running.add(pairs_csr_resident(dev, geo, cols, n, zero_based=zero_based))
         if timings is not None:

@@ -24,6 +24,7 @@ const char* status_name(int s)
     case csz::kInputEnd: return "input exhausted";
     case csz::kBadChecksum: return "Adler-32 mismatch";
     case csz::kBadChunk: return "unfiltered chunk of the wrong size";
+    case csz::kTrailing: return "bytes behind the end of the stream";
     }
     return "unknown status";
 }
@@ -103,6 +104,80 @@ int cs_inflate_chunks(cs_ctx* ctx, void* stream_, const void* d_file, int64_t fi
     if (failed)
         return fail(ctx, CS_ERR_CORRUPT, "cs_inflate_chunks: %lld of %lld chunks failed; the first is chunk %lld (%s)", (long long)failed,
                     (long long)n_chunks, (long long)first, status_name(h_status[first]));
+    return CS_OK;
+}
+
+int64_t cs_bgzf_max_block_bytes(void) { return (int64_t)csz::kMaxBgzfBlockBytes; }
+
+int cs_bgzf_inflate(cs_ctx* ctx, void* stream_, const void* d_file, int64_t file_bytes, const int64_t* h_offsets, const int64_t* h_nbytes,
+                    const int64_t* h_out_offsets, const int64_t* h_isizes, int64_t n_blocks, void* d_text, int64_t text_bytes, int32_t* h_status,
+                    int64_t* h_last_newline)
+{
+    CS_ENTER(ctx);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_blocks < 0 || file_bytes < 0 || text_bytes < 0) return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: negative size");
+    if (!h_last_newline) return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: null argument");
+    if (n_blocks >= (int64_t)std::numeric_limits<int>::max()) return fail(ctx, CS_ERR_UNSUPPORTED, "cs_bgzf_inflate: 2^31 - 1 blocks or more");
+    *h_last_newline = -1;
+    if (n_blocks == 0) return CS_OK;
+    if (!d_file || !h_offsets || !h_nbytes || !h_out_offsets || !h_isizes || !h_status || (!d_text && text_bytes > 0))
+        return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: null argument");
+    std::vector<csz::BgzfDesc> desc((size_t)n_blocks);
+    std::vector<std::pair<int64_t, int64_t>> spans;              // (start, end) of every block's text that is not empty
+    spans.reserve((size_t)n_blocks);
+    for (int64_t b = 0; b < n_blocks; ++b) {
+        const int64_t off = h_offsets[b], nb = h_nbytes[b], out = h_out_offsets[b], isize = h_isizes[b];
+        // the body and the four bytes of its CRC-32 behind it
+        if (off < 0 || nb < 0 || nb > (int64_t)std::numeric_limits<uint32_t>::max() || off > file_bytes || nb + 4 > file_bytes - off)
+            return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: block %lld (offset %lld, %lld bytes and its CRC-32) leaves the buffer of %lld bytes",
+                        (long long)b, (long long)off, (long long)nb, (long long)file_bytes);
+        if (isize < 0) return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: block %lld holds %lld bytes", (long long)b, (long long)isize);
+        if (isize > (int64_t)csz::kMaxBgzfBlockBytes)
+            return fail(ctx, CS_ERR_UNSUPPORTED, "cs_bgzf_inflate: block %lld holds %lld bytes, the limit is %u (cs_bgzf_max_block_bytes)", (long long)b,
+                        (long long)isize, csz::kMaxBgzfBlockBytes);
+        if (out < 0 || out > text_bytes || isize > text_bytes - out)
+            return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: block %lld (text offset %lld, %lld bytes) leaves the text buffer of %lld bytes",
+                        (long long)b, (long long)out, (long long)isize, (long long)text_bytes);
+        if (isize > 0) spans.emplace_back(out, out + isize);
+        desc[(size_t)b] = {(uint64_t)off, (uint64_t)out, (uint32_t)nb, (uint32_t)isize};
+        h_status[b] = csz::kOk;
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].first < spans[i - 1].second)
+            return fail(ctx, CS_ERR_INVALID, "cs_bgzf_inflate: the texts of two blocks overlap at offset %lld", (long long)spans[i].first);
+
+    CallBuffers Bf;
+    csz::BgzfDesc* d_desc = nullptr;
+    int32_t* d_status = nullptr;
+    long long* d_last = nullptr;
+    CS_HIP(ctx, Bf.get(&d_desc, (size_t)n_blocks));
+    CS_HIP(ctx, Bf.get(&d_status, (size_t)n_blocks));
+    CS_HIP(ctx, Bf.get(&d_last, 1));
+    long long last = -1;
+    CS_HIP(ctx, hipMemcpyAsync(d_desc, desc.data(), (size_t)n_blocks * sizeof(csz::BgzfDesc), hipMemcpyHostToDevice, stream));
+    CS_HIP(ctx, hipMemcpyAsync(d_last, &last, sizeof(last), hipMemcpyHostToDevice, stream));
+    csz::BgzfArgs A = {};
+    A.file = (const uint8_t*)d_file;
+    A.blocks = d_desc;
+    A.status = d_status;
+    A.text = (uint8_t*)d_text;
+    A.last_newline = d_last;
+    A.n_blocks = (int)n_blocks;
+    CS_HIP(ctx, csz::launch_bgzf_inflate(A, ctx->n_cu, stream));
+    CS_HIP(ctx, hipMemcpyAsync(h_status, d_status, (size_t)n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipMemcpyAsync(&last, d_last, sizeof(last), hipMemcpyDeviceToHost, stream));
+    CS_HIP(ctx, hipStreamSynchronize(stream));
+    *h_last_newline = (int64_t)last;
+    int64_t failed = 0, first = -1;
+    for (int64_t b = 0; b < n_blocks; ++b)
+        if (h_status[b] != csz::kOk) {
+            if (first < 0) first = b;
+            ++failed;
+        }
+    if (failed)
+        return fail(ctx, CS_ERR_CORRUPT, "cs_bgzf_inflate: %lld of %lld blocks failed; the first is block %lld (%s)", (long long)failed,
+                    (long long)n_blocks, (long long)first, h_status[first] == csz::kBadChecksum ? "CRC-32 mismatch" : status_name(h_status[first]));
     return CS_OK;
 }
 

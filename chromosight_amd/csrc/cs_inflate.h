@@ -29,6 +29,26 @@ struct InflateArgs {
 
 hipError_t launch_inflate(const InflateArgs& A, int n_cu, hipStream_t stream);
 
+constexpr uint32_t kMaxBgzfBlockBytes = 64u * 1024u;   // cs_bgzf_max_block_bytes(): the most text a BGZF member holds
+
+struct BgzfDesc {
+    uint64_t offset;       // of the member's deflate body in the buffer of file bytes; its CRC-32 stands in the 4 bytes behind the body
+    uint64_t out_offset;   // of its text in the text buffer
+    uint32_t nbytes;       // of the body
+    uint32_t isize;        // of its text
+};
+
+struct BgzfArgs {
+    const uint8_t* file;
+    const BgzfDesc* blocks;
+    int32_t* status;               // per block: csz::Status
+    uint8_t* text;
+    long long* last_newline;       // the largest offset in text of a '\n' written, by atomicMax (the caller stores -1 first)
+    int n_blocks;
+};
+
+hipError_t launch_bgzf_inflate(const BgzfArgs& A, int n_cu, hipStream_t stream);
+
 struct TableStats {
     unsigned long long flags;      // bit 0: an id outside [0, n_bins); bit 1: a pixel not behind the one before it; bit 2: a pixel below the diagonal
     long long count_min, count_max;

@@ -10,6 +10,14 @@
 //                       consecutive lanes to consecutive elements, clipped to the column's length (the last chunk is padded).  A
 //                       filter the chunk's mask skips is left out.  A chunk that fails stores its status and nothing else.
 //                       LDS: the tables (csz::Tables, 3.6 KB) and the chunk, so a 15 KB chunk runs eight waves per CU.
+//   bgzf_inflate_kernel one wave per member of a BGZF file (cs_bgzf_inflate), members taken round robin: the raw deflate body is decoded
+//                       into LDS by csz::inflate_member, which holds it to the member's ISIZE and CRC-32 (a byte table in LDS, every
+//                       lane the remainder of a contiguous share, shifted to the end and xor-reduced), and leaves LDS for
+//                       text[out_offset .. out_offset + isize) at any byte offset: byte stores in front of and behind the 16-byte
+//                       lines of the text buffer, one 16-byte store per whole line, never a read of it -- the neighbouring bytes of a
+//                       line belong to another wave.  The offset of the block's last '\n' goes into one int64 by atomicMax.  A
+//                       member that fails stores its status and nothing else.  LDS: tables, CRC table and 64 KiB of text, 69 KiB:
+//                       two waves per CU.
 //   table_check_kernel  one thread per pixel over bin1_id / bin2_id / count as stored (int32 / int64): ids in [0, n_bins), strictly
 //                       behind the pixel before it, on or above the diagonal; smallest and largest count; the column bin narrowed to
 //                       int32; and the row pointers: a pixel whose row r differs from the row q of the one before it is the first of
@@ -37,6 +45,12 @@ struct WaveCoop {
     {
 #pragma unroll
         for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor((unsigned long long)v, d);
+        return v;
+    }
+    __device__ __forceinline__ uint32_t xor_all(uint32_t v) const
+    {
+#pragma unroll
+        for (int d = kWave / 2; d > 0; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d);
         return v;
     }
 };
@@ -92,6 +106,65 @@ __global__ __launch_bounds__(kWave) void inflate_kernel(InflateArgs A)
         }
         if (threadIdx.x == 0) A.status[c] = status;
         __syncthreads();                                         // the next chunk overwrites buf
+    }
+}
+
+constexpr uint32_t kCrcTableBytes = 256u * sizeof(uint32_t);
+constexpr uint32_t kBgzfTextBytes = kMaxBgzfBlockBytes + 16u;      // a line more than a block: the copy-out reads whole words
+constexpr uint32_t kBgzfLds = kTableBytes + kCrcTableBytes + kBgzfTextBytes;
+
+__global__ __launch_bounds__(kWave) void bgzf_inflate_kernel(BgzfArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    Tables* T = (Tables*)lds;
+    uint32_t* crc_table = (uint32_t*)(lds + kTableBytes);
+    uint8_t* buf = lds + kTableBytes + kCrcTableBytes;
+    const uint32_t lane = threadIdx.x;
+    WaveCoop co;
+    for (int b = blockIdx.x; b < A.n_blocks; b += gridDim.x) {
+        const BgzfDesc d = A.blocks[b];
+        const uint8_t* in = A.file + d.offset;
+        uint32_t crc = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) crc |= (uint32_t)in[(uint64_t)d.nbytes + i] << (8u * i);
+        const int status = inflate_member(in, d.nbytes, buf, d.isize, co.uni(crc), T, crc_table, co);
+        __syncthreads();
+        const uint32_t n = d.isize;
+        if (status == kOk && n != 0) {
+            // to[0 .. n) = buf[0 .. n): the bytes in front of the first 16-byte line of `to` and behind its last whole one as byte
+            // stores, the lines between as one store each, their words put together from the aligned words of buf
+            uint8_t* to = A.text + d.out_offset;
+            uint32_t head = (uint32_t)((0u - (uintptr_t)to) & 15u);
+            if (head > n) head = n;
+            const uint32_t lines = (n - head) / 16u, tail = head + 16u * lines;
+            if (lane < head) to[lane] = buf[lane];
+            const uint32_t shift = 8u * (head & 3u);
+            const uint32_t* words = (const uint32_t*)(buf + (head & ~3u));
+            for (uint32_t k = lane; k < lines; k += kWave) {
+                uint32_t w[5];
+#pragma unroll
+                for (int j = 0; j < 5; ++j) w[j] = words[4u * k + j];            // (w[4]: at most 4 bytes behind buf[n), inside buf)
+                uint4 v;
+                v.x = (uint32_t)((((uint64_t)w[1] << 32) | w[0]) >> shift);
+                v.y = (uint32_t)((((uint64_t)w[2] << 32) | w[1]) >> shift);
+                v.z = (uint32_t)((((uint64_t)w[3] << 32) | w[2]) >> shift);
+                v.w = (uint32_t)((((uint64_t)w[4] << 32) | w[3]) >> shift);
+                *(uint4*)(to + head + 16u * k) = v;
+            }
+            if (lane < n - tail) to[tail + lane] = buf[tail + lane];
+            // the last '\n' of the block, looked for from its end, 64 bytes at a time: lane 0 has the last byte
+            for (uint32_t end = n;; end -= kWave) {
+                const bool hit = lane < end && buf[end - 1u - lane] == (uint8_t)'\n';
+                const unsigned long long hits = __ballot(hit);
+                if (hits != 0ull) {
+                    if (lane == 0) atomicMax(A.last_newline, (long long)(d.out_offset + end - (uint32_t)__ffsll(hits)));
+                    break;
+                }
+                if (end <= (uint32_t)kWave) break;
+            }
+        }
+        if (lane == 0) A.status[b] = status;
+        __syncthreads();                                         // the next block overwrites buf
     }
 }
 
@@ -165,6 +238,17 @@ hipError_t launch_inflate(const InflateArgs& A, int n_cu, hipStream_t stream)
     const long long resident = (long long)(n_cu > 0 ? n_cu : 1) * (per_cu < 1 ? 1 : per_cu > 32 ? 32 : per_cu);
     const int grid = (int)(A.n_chunks < resident ? A.n_chunks : resident);
     hipLaunchKernelGGL(inflate_kernel, dim3(grid), dim3(kWave), lds, stream, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_bgzf_inflate(const BgzfArgs& A, int n_cu, hipStream_t stream)
+{
+    if (A.n_blocks <= 0) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute((const void*)bgzf_inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+    const long long resident = (long long)(n_cu > 0 ? n_cu : 1) * (long long)((160u * 1024u) / kBgzfLds);      // two workgroups per CU
+    const int grid = (int)(A.n_blocks < resident ? A.n_blocks : resident);
+    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(kWave), kBgzfLds, stream, A);
     return hipGetLastError();
 }
 

@@ -1,13 +1,14 @@
-// cs_inflate_core.h -- the zlib stream decoder of cs_inflate.hip (RFC 1950 header, RFC 1951 body, Adler-32 trailer) as one
-// __host__ __device__ function over plain pointers and sizes.  The same control flow serves a wave on the device (cs_inflate.hip:
-// the stream's output and the decode tables live in LDS) and one thread on the host (tools/inflate_check.cpp, built with the
+// cs_inflate_core.h -- the decoders of cs_inflate.hip as __host__ __device__ functions over plain pointers and sizes: inflate_raw (the
+// blocks of RFC 1951), inflate_stream (a zlib stream: RFC 1950 header, that body, Adler-32 trailer) and inflate_member (the body of a
+// BGZF member against its ISIZE and CRC-32).  The same control flow serves a wave on the device (cs_inflate.hip:
+// the stream's output and the decode tables live in LDS) and one thread on the host (tools/inflate_check.cpp and tools/bgzf_check.cpp, built with the
 // sanitizers): whatever is done by "the lanes" goes through a small trait,
 //
-//   struct Coop { int lane(); int lanes(); void sync(); uint32_t uni(uint32_t); uint64_t sum(uint64_t); };
+//   struct Coop { int lane(); int lanes(); void sync(); uint32_t uni(uint32_t); uint64_t sum(uint64_t); uint32_t xor_all(uint32_t); };
 //
 // lane / lanes: who I am among the lanes that run this call together; sync: everything the lanes have stored is visible to all of
 // them; uni: a value that is the same in every lane, said so (the device takes it from the first lane, which lets the compiler keep
-// the bit reader in scalar registers); sum: the sum of a value over the lanes, in every lane.
+// the bit reader in scalar registers); sum / xor_all: the sum / the exclusive or of a value over the lanes, in every lane.
 //
 // Every lane runs the symbol loop with the same values, so every branch is uniform and every sync is reached by all lanes.  Lane 0
 // stores literals and table heads; match copies, stored blocks, table fills and the checksum are spread over the lanes.
@@ -38,8 +39,9 @@ enum Status : int32_t {
     kTooLong = 6,          // more than chunk_bytes of output
     kTooShort = 7,         // the stream ended with less
     kInputEnd = 8,         // the input ended inside the stream
-    kBadChecksum = 9,      // Adler-32
-    kBadChunk = 10         // cs_inflate.hip: a chunk without gzip whose stored size is not chunk_bytes
+    kBadChecksum = 9,      // Adler-32 (a zlib stream), CRC-32 (a BGZF member)
+    kBadChunk = 10,        // cs_inflate.hip: a chunk without gzip whose stored size is not chunk_bytes
+    kTrailing = 11         // a BGZF member: bytes of the body span behind the end of the stream
 };
 
 constexpr int kLitBits = 10, kDistBits = 8;      // index bits of the two one-step tables
@@ -224,17 +226,14 @@ CS_INF_HD uint32_t adler32(Coop& co, const uint8_t* out, uint32_t n)
     return (s2 << 16) | s1;
 }
 
-// One zlib stream in[0 .. nbytes) into out[0 .. cap): exactly cap bytes, or a status.  Bytes behind the trailer are not looked at
-// (zlib.decompress does not either).  cap < 2^24.
+// The blocks of one raw deflate stream (RFC 1951) from the reader's place into out[0 .. cap): kOk with the bytes decoded in *n_out and
+// the reader behind the last bit of the final block, or a status (kTooLong: the stream holds more than cap bytes).  cap < 2^24.
 template <typename Coop>
-CS_INF_HD int inflate_stream(const uint8_t* in, uint64_t nbytes, uint8_t* out, uint32_t cap, Tables* T, Coop& co)
+CS_INF_HD int inflate_raw(BitReader& br, uint8_t* out, uint32_t cap, uint32_t* n_out, Tables* T, Coop& co)
 {
-    BitReader br = {in, nbytes, 0, 0, 0};
+    const uint8_t* in = br.in;
+    const uint64_t nbytes = br.nbytes;
     uint32_t v = 0;
-    if (!take(br, co, 16, &v)) return kInputEnd;
-    const uint32_t cmf = v & 255u, flg = v >> 8;
-    if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 32u)) return kBadHeader;
-
     uint32_t at = 0;
     for (bool last = false; !last;) {
         if (!take(br, co, 3, &v)) return kInputEnd;
@@ -353,6 +352,22 @@ CS_INF_HD int inflate_stream(const uint8_t* in, uint64_t nbytes, uint8_t* out, u
             at += len;
         }
     }
+    *n_out = at;
+    return kOk;
+}
+
+// One zlib stream in[0 .. nbytes) into out[0 .. cap): exactly cap bytes, or a status.  Bytes behind the trailer are not looked at
+// (zlib.decompress does not either).  cap < 2^24.
+template <typename Coop>
+CS_INF_HD int inflate_stream(const uint8_t* in, uint64_t nbytes, uint8_t* out, uint32_t cap, Tables* T, Coop& co)
+{
+    BitReader br = {in, nbytes, 0, 0, 0};
+    uint32_t v = 0;
+    if (!take(br, co, 16, &v)) return kInputEnd;
+    const uint32_t cmf = v & 255u, flg = v >> 8;
+    if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 32u)) return kBadHeader;
+    uint32_t at = 0;
+    if (int rc = inflate_raw(br, out, cap, &at, T, co)) return rc;
     if (at != cap) return kTooShort;
     // the trailer: byte-aligned, big-endian
     br.drop(br.bits & 7);
@@ -365,4 +380,84 @@ CS_INF_HD int inflate_stream(const uint8_t* in, uint64_t nbytes, uint8_t* out, u
     return adler32(co, out, cap) == want ? kOk : kBadChecksum;
 }
 
+// ---- CRC-32 (IEEE 802.3, reflected: zlib.crc32) in two parts that combine ---------------------------------------------------------------
+// A register value is a polynomial over GF(2) modulo P with bit 31 the coefficient of x^0 (the reflected form).  The remainder of
+// a span is what the byte-table loop leaves in a register that started at zero, without the final inversion: linear in the bytes,
+// so the remainder of A followed by B is (remainder of A) * x^(8 |B|) + (remainder of B).
+constexpr uint32_t kCrcPoly = 0xEDB88320u;
+
+// entry i of the byte table
+CS_INF_HD uint32_t crc32_table_entry(uint32_t i)
+{
+    uint32_t r = i;
+    for (int k = 0; k < 8; ++k) r = (r >> 1) ^ (kCrcPoly & (0u - (r & 1u)));
+    return r;
+}
+
+// the remainder of p[0 .. n) through the 256-entry table
+CS_INF_HD uint32_t crc32_span(const uint32_t* table, const uint8_t* p, uint32_t n)
+{
+    uint32_t r = 0;
+    for (uint32_t i = 0; i < n; ++i) r = table[(r ^ p[i]) & 255u] ^ (r >> 8);
+    return r;
+}
+
+// a * b mod P
+CS_INF_HD uint32_t crc32_mul(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (int k = 31; k >= 0; --k) {                              // the coefficient of x^(31 - k) of a
+        p ^= b & (0u - ((a >> k) & 1u));
+        b = (b >> 1) ^ (kCrcPoly & (0u - (b & 1u)));             // b * x
+    }
+    return p;
+}
+
+// r * x^(8 n) mod P: the remainder r of a span once n more bytes stand behind it.  Square and multiply over the bits of n.
+CS_INF_HD uint32_t crc32_shift(uint32_t r, uint32_t n)
+{
+    uint32_t power = 0x00800000u;                                // x^8
+    for (; n != 0; n >>= 1) {
+        if (n & 1u) r = crc32_mul(r, power);
+        if (n > 1u) power = crc32_mul(power, power);
+    }
+    return r;
+}
+
+// where lane `lane` of `lanes` starts in n bytes cut into contiguous shares: a whole number of 4-byte words each, an odd number of
+// them (the lanes' reads of their k-th word then fall into different banks of the LDS), the last share that is not empty shorter
+CS_INF_HD uint32_t crc32_share_start(uint32_t n, int lane, int lanes)
+{
+    const uint32_t words = ((n + (uint32_t)lanes - 1u) / (uint32_t)lanes + 3u) / 4u;
+    const uint64_t at = (uint64_t)(words | 1u) * 4u * (uint32_t)lane;
+    return at < n ? (uint32_t)at : n;
+}
+
+// CRC-32 of out[0 .. n) as zlib.crc32 gives it; table: room for 256 entries, built here by the lanes
+template <typename Coop>
+CS_INF_HD uint32_t crc32(Coop& co, uint32_t* table, const uint8_t* out, uint32_t n)
+{
+    for (int i = co.lane(); i < 256; i += co.lanes()) table[i] = crc32_table_entry((uint32_t)i);
+    co.sync();
+    const uint32_t lo = crc32_share_start(n, co.lane(), co.lanes()), hi = crc32_share_start(n, co.lane() + 1, co.lanes());
+    uint32_t r = crc32_shift(crc32_span(table, out + lo, hi - lo), n - hi);
+    if (co.lane() == 0) r ^= crc32_shift(0xFFFFFFFFu, n);        // the initial value, n bytes on
+    return ~co.xor_all(r);
+}
+
+// One member of a BGZF file: the raw deflate body in[0 .. nbytes) into out[0 .. isize).  kOk when the body decodes to exactly isize
+// bytes, its final block ends inside the last byte of the span and the CRC-32 of the output is `crc`; kTooLong / kTooShort against
+// isize, kTrailing for whole bytes of the span behind the end of the stream, kBadChecksum for the CRC.  isize < 2^24.
+template <typename Coop>
+CS_INF_HD int inflate_member(const uint8_t* in, uint64_t nbytes, uint8_t* out, uint32_t isize, uint32_t crc, Tables* T, uint32_t* crc_table,
+                             Coop& co)
+{
+    BitReader br = {in, nbytes, 0, 0, 0};
+    uint32_t at = 0;
+    if (int rc = inflate_raw(br, out, isize, &at, T, co)) return rc;
+    if (at != isize) return kTooShort;
+    if (br.pos - (uint64_t)(br.bits >> 3) != nbytes) return kTrailing;          // (whole bytes the reader holds were not used)
+    co.sync();
+    return crc32(co, crc_table, out, isize) == crc ? kOk : kBadChecksum;
+}
 }  // namespace csz

@@ -580,6 +580,38 @@ def run_inflate_chunks(dev, buf, index, out=None, stream=None):
     return column, status[:n]
 
 
+BGZF_STATUS = INFLATE_STATUS[:9] + ("CRC-32 mismatch", INFLATE_STATUS[10], "bytes behind the end of the stream")
+
+
+def bgzf_max_block_bytes():
+    """The most text cs_bgzf_inflate takes from one member (cs_bgzf_max_block_bytes; no GPU needed)."""
+    return int(_lib.load_library().cs_bgzf_max_block_bytes())
+
+
+@_one_call_per_context
+def run_bgzf_inflate(dev, d_file, file_bytes, offsets, nbytes, out_offsets, isizes, d_text, text_bytes, stream=None):
+    """Inflate members of a BGZF file on the device (cs_bgzf_inflate).  d_file: a DeviceBuffer holding file_bytes bytes of the file
+    (never written); per member its body's offset and size in d_file, the offset of its text in d_text (a DeviceBuffer of at least
+    text_bytes bytes; any byte offset) and its ISIZE.  Returns (status, last_newline): the per-member codes (indices into BGZF_STATUS)
+    and the largest offset of a '\\n' written, -1 for none.  ValueError for a member that leaves d_file or d_text and for texts that
+    overlap, NotImplementedError for an ISIZE beyond bgzf_max_block_bytes(), CorruptChunks when members failed (every other member
+    is in d_text)."""
+    arrays = [np.ascontiguousarray(a, dtype=np.int64) for a in (offsets, nbytes, out_offsets, isizes)]
+    n = int(arrays[0].size)
+    if any(a.ndim != 1 or a.size != n for a in arrays):
+        raise ValueError("the per-member arrays differ in length")
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    last = C.c_int64(-1)
+    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))          # noqa: E731
+    rc = dev.lib.cs_bgzf_inflate(dev.ctx, stream, d_file.ptr if d_file is not None else None, int(file_bytes), *[i64(a) for a in arrays], n,
+                                 d_text.ptr if d_text is not None else None, int(text_bytes), status.ctypes.data_as(C.POINTER(C.c_int32)),
+                                 C.byref(last))
+    if rc == CS_ERR_CORRUPT:
+        raise CorruptChunks(dev.lib.cs_last_error(dev.ctx).decode("utf-8", "replace"), status[:n])
+    dev._check(rc)
+    return status[:n], int(last.value)
+
+
 @_one_call_per_context
 def run_table_from_columns(dev, bin1, bin2, count, nnz, n_bins, stream=None):
     """The finish pass over the decoded columns (cs_table_from_columns_count / _fill): bin1, bin2 (DeviceBuffers of int32 or int64, the

@@ -505,7 +505,7 @@ class DeviceCool:
         return pairs_device(chunks, chromsizes, binsize, zero_based=zero_based, dev=dev)
 
     @classmethod
-    def from_pairs_file(cls, path, binsize, chromsizes=None, *, zero_based=False, parse="auto", piece_bytes=None, dev=None):
+    def from_pairs_file(cls, path, binsize, chromsizes=None, *, zero_based=False, parse="auto", piece_bytes=None, dev=None, inflate="auto"):
         """from_pairs for a 4DN .pairs / .pairs.gz file.  chromsizes: ordered name -> length in bp; None takes the #chromsize: lines
         of the file.  parse: where the text becomes columns.  "host": io.read_pairs (pandas), chunk by chunk into from_pairs.
         "device": the header pass stays on the host; the body goes to HBM in pieces of about `piece_bytes` (default
@@ -515,18 +515,44 @@ class DeviceCool:
         length, positions of 1 to 18 digits, no empty line); DevicePairsRefused (a ValueError) names the first line it flags.
         "auto": the device when AUTO_PARSE_ON_DEVICE says so, and the host reader for the whole file -- its table, its `.dropped`
         and its exceptions -- as soon as the device route raises a ValueError.  CHROMOSIGHT_HIP_HOST_PARSE=1 in the environment
-        forces the host route (ValueError together with parse="device")."""
+        forces the host route (ValueError together with parse="device").
+        inflate: where a .gz on the device route becomes text.  "host": zlib on one host thread, as a stream.  "device": the file
+        must be what bgzip writes (BGZF: gzip members of at most 64 KiB of text that state their own size, back to back from the
+        first byte to the last, cload.bgzf_blocks); its members go to HBM as they are and are inflated there (cs_bgzf_inflate), so
+        the host sees the header's members only.  DeviceInflateRefused (a ValueError) for any other .gz; engine.CorruptChunks names
+        the first member that does not decode (index, file offset, status).  ValueError with parse="host", with a path that is
+        not .gz.  "auto": the device for a qualifying file when AUTO_INFLATE_ON_DEVICE says so; a file that is refused or holds a
+        corrupt member is read again from its start with the host's zlib, which raises what it raises.
+        CHROMOSIGHT_HIP_HOST_INFLATE=1 in the environment forces the host (ValueError together with inflate="device").  Every
+        route gives the same table, bit for bit."""
         from . import cload, io as cio
+        from .engine import CorruptChunks
         route = _parse_route(parse)
+        inflate_route = _inflate_route(inflate)
+        is_gz = os.fsdecode(path).endswith(".gz")
+        if inflate_route == "device":
+            if route == "host":
+                raise ValueError("inflate='device' inflates for the device parser: it does not go with parse='host'")
+            if not is_gz:
+                raise ValueError(f"inflate='device' takes a .gz file, got {path!r}")
         if piece_bytes is not None and (isinstance(piece_bytes, bool) or int(piece_bytes) != piece_bytes or int(piece_bytes) < 1):
             raise ValueError(f"piece_bytes must be a positive integer, got {piece_bytes!r}")
         pairs_file = cio.read_pairs(path, chromsizes)
+        attempts = []                                   # of the device parser: over text inflated on the device, on the host
         if route != "host":
+            attempts += ["device"] if is_gz and inflate_route != "host" else []
+            attempts += ["host"] if inflate_route != "device" else []
+        for how in attempts:
             try:
-                return cload.pairs_file_device(pairs_file, binsize, zero_based=zero_based, piece_bytes=piece_bytes, dev=dev)
-            except (ValueError, EOFError, zlib.error):          # (DevicePairsRefused is a ValueError)
+                return cload.pairs_file_device(pairs_file, binsize, zero_based=zero_based, piece_bytes=piece_bytes, dev=dev, inflate=how)
+            except (ValueError, EOFError, zlib.error) as exc:   # (DevicePairsRefused and the two below are ValueErrors)
+                if how == "device" and isinstance(exc, (DeviceInflateRefused, CorruptChunks)):
+                    if inflate_route == "device":
+                        raise
+                    continue                            # "auto": the host inflates
                 if route == "device":
                     raise
+                break
         return cls.from_pairs(pairs_file, pairs_file.chromsizes, binsize, zero_based=zero_based, dev=dev)
 
     @classmethod
@@ -1518,6 +1544,20 @@ def _parse_route(parse):
     return _route("parse", parse, "CHROMOSIGHT_HIP_HOST_PARSE", AUTO_PARSE_ON_DEVICE)
 
 
+class DeviceInflateRefused(ValueError):
+    """The .gz is not what bgzip writes (DeviceCool.from_pairs_file, open_pairs(inflate="device"))."""
+
+
+AUTO_INFLATE_ON_DEVICE = True       # what open_pairs(inflate="auto") does with a bgzip-compressed .pairs.gz (tools/time_pairs_bgzf.py: on
+                                    # both inputs the device route lies below the host inflate of the commit before by far more than
+                                    # that one's run-to-run spread, profiles/pairs_bgzf_time.json)
+
+
+def _inflate_route(inflate):
+    """open_pairs' `inflate`: _route."""
+    return _route("inflate", inflate, "CHROMOSIGHT_HIP_HOST_INFLATE", AUTO_INFLATE_ON_DEVICE)
+
+
 def device_decode_refusal(indexes, max_chunk_bytes):
     """Why the pixel columns of a file are not decoded on the device, or None when they are.  indexes: name -> hdf5_lite.ChunkIndex
     of pixels/bin1_id, bin2_id and count (None: not a chunked dataset); max_chunk_bytes: engine.inflate_max_chunk_bytes()."""
@@ -1659,7 +1699,7 @@ def open_cool(uri_or_cool, *, norm="auto", inter=False, n_mads=5, balance="weigh
 
 
 def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, norm="auto", inter=False, n_mads=5, dev=None,
-               resolution=None, parse="auto", piece_bytes=None):
+               resolution=None, parse="auto", piece_bytes=None, inflate="auto"):
     """Read pairs (a 4DN .pairs / .pairs.gz path, or an iterable of (chrom1, pos1, chrom2, pos2) chunks of arrays as
     io.read_pairs yields them) binned at `binsize` bp on the device (DeviceCool.from_pairs: what `cooler cload pairs` writes, which
     the reference expects to have been run beforehand) and given weights as open_cool gives them to a file without stored ones:
@@ -1669,16 +1709,20 @@ def open_pairs(path_or_chunks, binsize, chromsizes=None, *, zero_based=False, no
     open_cool.  `.dropped` is the number of pairs left out for a chromosome that is not in `chromsizes`.  The binning is exact, so
     every rank of a parallel run that bins its own copy gets the same table and weights.
     parse, piece_bytes: where the text of a file becomes columns, as in DeviceCool.from_pairs_file ("auto", "host" or "device"; both
-    routes give the same table, bit for bit).  Chunks are parsed already: anything but "auto" with them is a ValueError."""
+    routes give the same table, bit for bit).  Chunks are parsed already: anything but "auto" with them is a ValueError.
+    inflate: where a .pairs.gz becomes text, as in DeviceCool.from_pairs_file ("auto", "host", or "device" for a file bgzip wrote);
+    anything but "auto" with chunks is a ValueError."""
     _check_norm(norm)
     geometry_binsize = int(binsize)
     factor = _resolution_factor(resolution, geometry_binsize)
     chunks = path_or_chunks
     if _is_path(chunks):                # (from_pairs_file checks `parse`)
         dcool = DeviceCool.from_pairs_file(chunks, geometry_binsize, chromsizes, zero_based=zero_based, parse=parse,
-                                           piece_bytes=piece_bytes, dev=dev)
+                                           piece_bytes=piece_bytes, dev=dev, inflate=inflate)
     elif parse != "auto":
         raise ValueError(f"parse={parse!r} takes files: chunks are parsed columns already")
+    elif inflate != "auto":
+        raise ValueError(f"inflate={inflate!r} takes files: chunks are parsed columns already")
     elif chromsizes is None:
         raise ValueError("open_pairs needs chromsizes for pairs that do not come from a file")
     else:

@@ -52,7 +52,7 @@ typedef enum {
     CS_ERR_RANGE = -5,     /* cs_normxcorr2_host, cs_normxcorr2 with cs_ctx_set_range_check: the map holds a non-finite pixel,
                               or magnitudes beyond what the float32 kernels square without overflow (1e15): evaluate it in
                               float64 (the Python shim does) */
-    CS_ERR_CORRUPT = -6    /* cs_inflate_chunks: at least one chunk of the file did not decode; see its per-chunk status */
+    CS_ERR_CORRUPT = -6    /* cs_inflate_chunks, cs_bgzf_inflate: at least one chunk / member did not decode; see the per-chunk status */
 } cs_status;
 
 enum { CS_F32 = 0, CS_F64 = 1, CS_U8 = 2 /* masks only */ };
@@ -573,6 +573,28 @@ int cs_table_from_columns_count(cs_ctx* ctx, void* stream, const void* d_bin1, c
                                 cs_table_report* h_report);
 int cs_table_from_columns_fill(cs_ctx* ctx, void* stream, const void* d_count, int32_t count_bytes, int64_t nnz, void* d_out_data,
                                int32_t dtype);
+
+/* ---- the members of a bgzip-compressed file (BGZF: independent gzip members of at most 64 KiB of text each) inflated from file bytes
+ * in HBM into one contiguous text buffer: what zlib does for a .pairs.gz on the host ----
+ * cs_bgzf_inflate decodes n_blocks (< 2^31 - 1) members.  d_file: file_bytes bytes of the file (any span of it) on the device; per
+ *   member, host arrays of the offset and size of its raw deflate body in d_file (what stands between the member's header and its
+ *   8-byte trailer), of the offset of its text in d_text (any byte offset) and of its ISIZE.  The expected CRC-32 is read on the
+ *   device from the four bytes directly behind the body (the head of the member's trailer), which must lie inside d_file too.  A body
+ *   that leaves d_file with those four bytes, a text that leaves d_text (text_bytes bytes), a negative size, or two texts that are not
+ *   empty and overlap: CS_ERR_INVALID; an ISIZE above cs_bgzf_max_block_bytes() (65 536): CS_ERR_UNSUPPORTED; all found on the host
+ *   before anything is launched.  A member succeeds when its body decodes to exactly ISIZE bytes, the final deflate block ends inside
+ *   the last byte of the body, and the CRC-32 of the text is the expected one.  h_status receives a code per member: 0, or 2 to 8 as
+ *   cs_inflate_chunks names them (6 and 7 against ISIZE), 9 CRC-32 mismatch, 11 bytes of the body behind the end of the stream.  A
+ *   member that fails writes nothing to d_text and stops no other; when any failed the call returns CS_ERR_CORRUPT and cs_last_error
+ *   names their number and the first.  Bytes of d_text that belong to no member are not touched: a member's text is stored with byte
+ *   stores at its unaligned ends and 16-byte stores between, never by reading d_text.  h_last_newline receives the largest offset in
+ *   d_text of a '\n' among the bytes written, -1 when there is none (an integer maximum: the same for every launch shape).
+ *   No body can make the kernel read outside its bytes and its CRC-32, or write outside its ISIZE bytes of text.  Synchronous; d_file
+ *   is never written. */
+int cs_bgzf_inflate(cs_ctx* ctx, void* stream, const void* d_file, int64_t file_bytes, const int64_t* h_offsets, const int64_t* h_nbytes,
+                    const int64_t* h_out_offsets, const int64_t* h_isizes, int64_t n_blocks, void* d_text, int64_t text_bytes,
+                    int32_t* h_status, int64_t* h_last_newline);
+int64_t cs_bgzf_max_block_bytes(void);
 
 /* ---- device-side foci: detection.py:387 pick_foci + the statistics of :18 validate_patterns ---- */
 typedef struct {
